@@ -6,7 +6,11 @@ pool the latents to 64x64, ControlNetModel.forward (K of them + router + merge i
 ControlNetAdapter.forward -- on synthetic latents / prompts / condition images already resident in HBM and seeded random
 weights of the real architectures (361 M + 184 M / 587 M parameters).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sdxl|svd16|i2vgen16|multi3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sdxl|svd16|i2vgen16|multi3] [--dump-outputs DIR]
+
+`--steps K` timed steps give `ms_per_step` (their mean).  `--dump-outputs DIR` writes what the last timed step returned as float32
+DIR/<name>.npy (a seeded sample of each tensor when they would exceed 56 MB together) so that two builds run with the same arguments
+-- same seeded inputs and weights -- can be compared output for output.
 
 `--gpus N` with N > 1 launches the N ranks itself (re-executes under `python -m torch.distributed.run`, one rank per
 GPU over RCCL, 127.0.0.1 rendezvous); started under a launcher already (RANK / WORLD_SIZE in the environment) it joins it.
@@ -168,6 +172,46 @@ def quick_time(dev, wname, batch, steps, warmup, world):
     return res
 
 
+DUMP_BUDGET_BYTES = 56 << 20      # --dump-outputs: all files together stay below 64 MB
+
+
+def step_outputs(out):
+    """(name, tensor) of what one step returns: ((controlnet down, mid), (adapter down, mid)); None entries are left out"""
+    (down, mid), (ad, ad_mid) = out
+    named = [("controlnet.down%02d" % i, v) for i, v in enumerate(down)] + [("controlnet.mid", mid)]
+    named += [("adapter.down%02d" % i, v) for i, v in enumerate(ad or [])] + [("adapter.mid", ad_mid)]
+    return [(k, v) for k, v in named if v is not None]
+
+
+def dump_outputs(out, path):
+    """--dump-outputs: every output tensor of one step as float32 .npy.  When they exceed DUMP_BUDGET_BYTES together, each keeps the
+    same share of its elements at sorted positions drawn from a generator seeded by crc32(name), so two builds run with the same
+    arguments sample the same positions.  manifest.json says, per file, the full shape and how many elements were kept."""
+    import zlib
+    import numpy as np
+    import torch
+    named = step_outputs(out)
+    total = sum(v.numel() for _, v in named)
+    frac = min(1.0, DUMP_BUDGET_BYTES / 4.0 / max(total, 1))
+    os.makedirs(path, exist_ok=True)
+    manifest = {}
+    for name, v in named:
+        flat = v.detach().reshape(-1)
+        if frac < 1.0:
+            seed = zlib.crc32(name.encode())
+            idx = np.unique(np.random.default_rng(seed).integers(0, flat.numel(), size=int(flat.numel() * frac)))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            sample = "seeded uniform positions (numpy default_rng(%d).integers, unique, sorted)" % seed
+        else:
+            sample = "all"
+        arr = flat.float().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), arr)
+        manifest[name] = {"shape": list(v.shape), "dtype": str(v.dtype).replace("torch.", ""), "numel": v.numel(),
+                          "kept": int(arr.size), "sample": sample}
+    with open(os.path.join(path, "manifest.json"), "w") as fh:
+        json.dump(manifest, fh, indent=1)
+
+
 def pmc_traffic_for(kernel_row):
     """HBM bytes per launch of one (symbol, grid) from the committed rocprofv3 PMC passes (cannot run inside the bench)"""
     tfiles = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_hbm_traffic*.json")))
@@ -225,7 +269,13 @@ def main():
     ap.add_argument("--fused", action="store_true",
                     help="time the fused controlled_step(controlnet, adapter, ...) instead of the pipelines' two calls "
                          "controlnet(...) ; adapter(...) (same arithmetic, bit-identical results)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0 writes what the last timed step returned (the ControlNet and adapter residuals) to DIR/<name>.npy in "
+                         "float32, a fixed seeded sample of each tensor when all of them exceed %d MB, plus DIR/manifest.json "
+                         "(e.g. bench_outputs/, git-ignored)" % (DUMP_BUDGET_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args))
@@ -324,10 +374,20 @@ def main():
             torch.cuda.synchronize()
             run = step
 
+    last_eager = [None]
+    if args.dump_outputs and mode == "eager":      # an eager step's outputs are fresh tensors: keep the last one's for the dump
+        def run_keep():
+            last_eager[0] = step()
+        run = run_keep
+
     for _ in range(args.warmup):
         run()
 
     elapsed = dp.timed_region(run, args.steps, device=dev)        # barrier + sync on both sides, MAX over ranks
+    if args.dump_outputs and rank == 0:            # what the last timed step wrote, before anything else runs on these plans
+        torch.cuda.synchronize()
+        dump_outputs(static_out if mode == "hipgraph" else last_eager[0], args.dump_outputs)
+        last_eager[0] = None
     ms_per_step = elapsed / args.steps * 1e3
     value = dp.aggregate_throughput(1, args.steps, elapsed, world)   # whole-job denoise-steps/s (each rank: its own batch / clip)
     if comm is not None:

@@ -154,13 +154,13 @@ def test_controlnet_nonsquare_single_image_golden(controlnet):
         check_digest(t, d, TOL, "controlnet[nonsquare] out %d" % i)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="needs the reference checkout (build container only)")
 def test_oracle_against_the_reference_files_live_random_configurations():
     """beyond the fixed goldens: randomly drawn adapter / ControlNet configurations, the reference's own files (over the diffusers
-    shim) against the oracle on the same seeded weights and inputs -- tests/golden/live_check.py, in its own process because it
-    installs the shim as `diffusers`"""
+    shim) against the oracle on the same seeded weights and inputs -- tests/golden/live_check.py, held to the reference's outputs
+    that `live_check.py 8 3000 --record` stored in tests/golden/live_random.pt, in its own process (it patches torch.Tensor.cuda)"""
     import subprocess
     import sys
-    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "live_check.py"), "8", "3000"],
+    gold = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    r = subprocess.run([sys.executable, os.path.join(gold, "live_check.py"), "8", "3000", "--stored", os.path.join(gold, "live_random.pt")],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and "LIVE CHECK OK: 8 cases" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
