@@ -74,6 +74,12 @@ class AdapterConfig(C.Structure):
                 ("loc_M", C.c_int32)]
 
 
+class TextEncoderConfig(C.Structure):
+    _fields_ = [("vocab_size", C.c_int32), ("hidden_size", C.c_int32), ("intermediate_size", C.c_int32),
+                ("num_hidden_layers", C.c_int32), ("num_attention_heads", C.c_int32), ("max_position_embeddings", C.c_int32),
+                ("eos_token_id", C.c_int32), ("layer_norm_eps", C.c_float)]
+
+
 CB_GATHER = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p)
 CB_REDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)
 CB_HALO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p)
@@ -103,6 +109,8 @@ EXPORTS = [
     "ctrl_adapter_forward_scatter", "ctrl_adapter_forward_clip_sharded", "ctrl_controlnet_text_cache", "ctrl_adapter_text_cache", "ctrl_controlnet_trim", "ctrl_adapter_trim", "ctrl_controlnet_selection", "ctrl_adapter_selection",
     "ctrl_step_forward", "ctrl_rccl_unique_id", "ctrl_rccl_comm_create", "ctrl_rccl_comm_destroy", "ctrl_rccl_comm_bind", "ctrl_rccl_comm_bytes_sent",
     "ctrl_router_weights", "ctrl_router_merge", "ctrl_prepare_images",
+    "ctrl_text_encoder_create", "ctrl_text_encoder_destroy", "ctrl_text_encoder_forward", "ctrl_text_encoder_id_status",
+    "ctrl_op_text_embed", "ctrl_op_text_attn", "ctrl_op_text_final_ln",
 ]
 
 _lib = None
@@ -120,7 +128,8 @@ def lib():
         _lib.ctrl_last_error.restype = C.c_char_p
         for name in EXPORTS:
             fn = getattr(_lib, name)
-            if name not in ("ctrl_last_error", "ctrl_policy_get", "ctrl_policy_name", "ctrl_controlnet_destroy", "ctrl_adapter_destroy", "ctrl_rccl_comm_destroy", "ctrl_rccl_comm_bytes_sent"):
+            if name not in ("ctrl_last_error", "ctrl_policy_get", "ctrl_policy_name", "ctrl_controlnet_destroy", "ctrl_adapter_destroy", "ctrl_rccl_comm_destroy", "ctrl_rccl_comm_bytes_sent",
+                            "ctrl_text_encoder_destroy"):
                 fn.restype = C.c_int
         _lib.ctrl_policy_get.restype = C.c_char_p
         _lib.ctrl_policy_get.argtypes = [C.c_char_p]
@@ -128,6 +137,14 @@ def lib():
         _lib.ctrl_policy_set.argtypes = [C.c_char_p, C.c_char_p]
         _lib.ctrl_controlnet_destroy.restype = None
         _lib.ctrl_adapter_destroy.restype = None
+        _lib.ctrl_text_encoder_destroy.restype = None
+        _lib.ctrl_op_text_embed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ctrl_op_text_attn.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]
+        _lib.ctrl_op_text_final_ln.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
+                                               C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.ctrl_text_encoder_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_int, C.c_void_p]
         _lib.ctrl_rccl_comm_destroy.restype = None
         _lib.ctrl_rccl_comm_destroy.argtypes = [C.c_void_p]
         _lib.ctrl_rccl_comm_bytes_sent.restype = C.c_int64

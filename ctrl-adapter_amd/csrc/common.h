@@ -80,6 +80,10 @@ __device__ __forceinline__ void store_from_f32(void* p, size_t i, int dt, float 
 }
 // v_rcp_f32 (1 ulp) instead of an IEEE division (~10 VALU): SiLU sits in GEMM epilogues and the GroupNorm apply pass
 __device__ __forceinline__ float silu_f(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+// x * sigmoid(k x) in the rcp / exp form of silu_f: the GEMM epilogue activations (ctrl_igemm_desc::act) 1 = SiLU (k = 1: -k * x is
+// exactly -x, the same value as silu_f) and 2 = quick_gelu (CLIP's hidden_act, k = 1.702) share one code path
+__device__ __forceinline__ float x_sigmoid_kx(float x, float k) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-k * x)); }
+__device__ __forceinline__ float act_k(int act) { return act == 2 ? 1.702f : 1.0f; }
 // exact (erf) GELU with erf from Abramowitz-Stegun 7.1.26 (|abs error| <= 1.5e-7, far below fp16 resolution).
 //   gelu(x) = x/2 * (1 + erf(x/sqrt2)),  erf(z) = sign(z) * (1 - P(t) e^{-z^2}),  t = 1/(1 + p|z|)
 //           = max(x, 0) - |x| * (P(t)/2) * e^{-x^2/2}            (x/2 + |x|/2 = max(x,0): no sign select, no 1 +/- erf)

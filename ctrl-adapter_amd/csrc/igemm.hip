@@ -785,7 +785,7 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(IGemmArgs a, const f
         for (int j = 0; j < 8; ++j) {
             if (a.bias) x[j] += a.bias[col + j];
             if (a.rowvec) x[j] += a.rowvec[(row / a.rows_per_img) * a.rowvec_ld + col + j];
-            if (a.act == 1) x[j] = silu_f(x[j]);
+            if (a.act) x[j] = x_sigmoid_kx(x[j], act_k(a.act));
         }
         if (a.res) {
             if (a.res_f32) {
@@ -1272,6 +1272,21 @@ int op_igemm(const IGemmArgs& a, hipStream_t s) {
     }
     TRY(igemm_validate(b));
     return igemm_dispatch(b, s);
+}
+
+// One fixed form for the text encoder (plan_text.cpp): the 64 x 64 x 64 tile at every M, never split-K, never grouped -- every output row
+// is then computed by the same instruction sequence whatever the batch, so a prompt encodes to the same bits alone or inside a batch
+// (dispatch() sizes the tile by M).  Row-major problems with Cin % 64 == 0 and the aligned vector epilogue only.
+int op_igemm_pinned(const IGemmArgs& a, hipStream_t s) {
+    IGemmArgs b = a;
+    b.splitk_ws = nullptr; b.splitk_ws_bytes = 0; b.splitk_tickets = nullptr;
+    if (!b.nonfinite && range_check_on()) {
+        b.nonfinite = range_flag();
+        CTRL_CHECK(b.nonfinite != nullptr, "igemm: the range check is on but its flag word could not be allocated");
+    }
+    TRY(igemm_validate(b));
+    CTRL_CHECK(b.mode == IG_ROWS && b.Cin % 64 == 0 && !b.geglu && can_swap(b), "igemm_pinned: needs an aligned row-major problem with Cin % 64 == 0");
+    return launch_cfg2<64, 64, 64, 2, 2, 3, IG_ROWS, true>(b, s);
 }
 
 // what has to agree for two problems to share a launch: every field the dispatcher, the launch geometry and the kernels' uniform

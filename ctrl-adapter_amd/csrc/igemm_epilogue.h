@@ -120,9 +120,10 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmArgs& e, f4 (&acc)[BM 
                         f4 x = acc[mi][ni] + b4;
                         if (row_w < e.M) {
                             if (e.rowvec) x += *(const f4*)(e.rowvec + (size_t)(row_w / e.rows_per_img) * e.rowvec_ld + pcol);
-                            if (e.act == 1) {
+                            if (e.act) {
+                                const float k = act_k(e.act);
 #pragma unroll
-                                for (int i = 0; i < 4; ++i) x[i] = silu_f(x[i]);
+                                for (int i = 0; i < 4; ++i) x[i] = x_sigmoid_kx(x[i], k);
                             }
                             if (Rptr) {
                                 if (e.res_f32) {
@@ -260,9 +261,10 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmArgs& e, f4 (&acc)[BM 
 #pragma unroll
                                 for (int i = 0; i < 4; ++i) x[i] *= gelu_erf_f(g[i]);
                             }
-                            if (e.act == 1) {
+                            if (e.act) {
+                                const float k = act_k(e.act);
 #pragma unroll
-                                for (int i = 0; i < 4; ++i) x[i] = silu_f(x[i]);
+                                for (int i = 0; i < 4; ++i) x[i] = x_sigmoid_kx(x[i], k);
                             }
                             const int lcol = (gg ? (ni >> 1) * 16 : ni * 16) + ecol;
                             const float sc = col_scale(e, wcol0 + lcol);
@@ -305,9 +307,10 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmArgs& e, f4 (&acc)[BM 
 #pragma unroll
                             for (int i = 0; i < 4; ++i) x[i] *= gelu_erf_f(g[i]);
                         }
-                        if (e.act == 1) {
+                        if (e.act) {
+                            const float k = act_k(e.act);
 #pragma unroll
-                            for (int i = 0; i < 4; ++i) x[i] = silu_f(x[i]);
+                            for (int i = 0; i < 4; ++i) x[i] = x_sigmoid_kx(x[i], k);
                         }
                         const int lcol = (gg ? (ni >> 1) * 16 : ni * 16) + ecol;
                         *(f4*)(stg + erow * SLD + lcol) = x;
@@ -443,7 +446,7 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmArgs& e, f4 (&acc)[BM 
                         const float g = acc[mi][ni + (NI > 1 ? 1 : 0)][i] + bg;
                         x = x * gelu_erf_f(g);
                     }
-                    if (e.act == 1) x = silu_f(x);
+                    if (e.act) x = x_sigmoid_kx(x, act_k(e.act));
                     if (Rptr && row < e.M)
                         x += e.res_f32 ? ((const float*)e.res)[res_row_of(e, row) * e.ldres + ocol] : (float)Rptr[res_row_of(e, row) * e.ldres + ocol];
                     v[i] = x * col_scale(e, ocol);

@@ -34,6 +34,8 @@ void igemm_tile_of(int bid, int ntm, int ntn, int mode, int group, int* tile_m, 
 constexpr int kMaxIGemmGroup = 4;
 constexpr int kMaxGroup = kMaxIGemmGroup;
 int op_igemm_group(const IGemmArgs* a, int n, hipStream_t s);
+// the same contraction in ONE fixed form whatever M (64 x 64 x 64 tile, no split-K, no grouping): batch-invariant rows (the text encoder)
+int op_igemm_pinned(const IGemmArgs& a, hipStream_t s);
 // Fused GEGLU feed-forward, dim 512 / hidden 2048 (ffn.hip; include/ctrl_hip.h: ctrl_ffn_desc): one launch instead of the GEGLU GEMM +
 // the K = 2048 GEMM; op_ffn_fused deposits into an installed collector like op_igemm does
 typedef ctrl_ffn_desc FfnArgs;
@@ -102,6 +104,16 @@ inline AttnGroup attn_grp_make(const AttnArgs& a) {
 }
 // instruction-selection variant of the head_dim-64 long-sequence kernel (attention_d64.hip); performance only
 int attn_set_variant(int v);
+
+// CLIP text encoder (text.hip): token + position embedding into the fp32 stream fused with the first LayerNorm (fp16 y; ids outside
+// [0, V) are clamped and raise *bad), causal self-attention over L <= 128 tokens straight from the [N*L][ld] Q | K | V rows (head_dim 64),
+// final LayerNorm into y_dt (+ the pooled row per prompt: argmax(ids) when eos == 2, else the first eos position), fp32 -> y_dt copy
+int op_text_embed(const int64_t* ids, const float* tok, const float* pos, int V, int N, int L, int C, float* x,
+                  const float* gamma, const float* beta, float eps, half_t* y, int* bad, hipStream_t s);
+int op_text_attn(const half_t* qkv, long ld, half_t* out, long ldo, int N, int L, int heads, float scale, hipStream_t s);
+int op_text_final(const void* x, int x_dt, int rows, int C, const float* gamma, const float* beta, float eps, void* y, int y_dt,
+                  const int64_t* ids, int L, int eos, void* pooled, hipStream_t s);
+int op_text_store(const float* x, void* y, int y_dt, size_t n, hipStream_t s);
 
 // temporal attention over the frame axis: tokens X [(b*F+f)*HW + p][...]; seq = F (<= 32)
 typedef ctrl_tattn_desc TAttnArgs;

@@ -1,0 +1,248 @@
+"""CLIPTextModel -- drop-in mirror of the SD-1.5 text encoder (transformers CLIPTextModel, the `text_encoder` that
+ControlNetHelper loads at model/ctrl_helper.py:34-41) whose forward runs in libctrlhip (csrc/text.hip, csrc/plan_text.cpp), and
+encode_controlnet_prompt -- ControlNetHelper.encode_controlnet_prompt (model/ctrl_helper.py:300-457) with the prompts and the
+negative prompts encoded in ONE forward.
+
+State-dict keys are the transformers 4.x layout SD-1.5's text_encoder/model.safetensors stores (`text_model.embeddings....`);
+the 5.x layout without the `text_model.` prefix loads as well."""
+import ctypes as C
+
+import torch
+from torch import nn
+
+from . import _lib as L
+from ._plan import Config, ParamTreeModule
+
+
+class CLIPTextOutput(tuple):
+    """(last_hidden_state, pooler_output[, hidden_states]) with attribute access, indexed like transformers'
+    BaseModelOutputWithPooling: [0] last hidden state, [1] pooled, [-1] the tuple of hidden states when they were asked for"""
+
+    def __new__(cls, last_hidden_state, pooler_output, hidden_states=None):
+        items = (last_hidden_state, pooler_output) + ((hidden_states,) if hidden_states is not None else ())
+        self = super().__new__(cls, items)
+        self.last_hidden_state, self.pooler_output, self.hidden_states = last_hidden_state, pooler_output, hidden_states
+        return self
+
+
+def text_encoder_spec(vocab_size, hidden_size, intermediate_size, num_hidden_layers, max_position_embeddings):
+    """(name, shape) of every parameter, transformers 4.x keys"""
+    C_, I = hidden_size, intermediate_size
+    spec = [("text_model.embeddings.token_embedding.weight", (vocab_size, C_)),
+            ("text_model.embeddings.position_embedding.weight", (max_position_embeddings, C_))]
+    for i in range(num_hidden_layers):
+        p = "text_model.encoder.layers.%d." % i
+        for proj in ("k_proj", "v_proj", "q_proj", "out_proj"):
+            spec += [(p + "self_attn.%s.weight" % proj, (C_, C_)), (p + "self_attn.%s.bias" % proj, (C_,))]
+        spec += [(p + "layer_norm1.weight", (C_,)), (p + "layer_norm1.bias", (C_,)),
+                 (p + "mlp.fc1.weight", (I, C_)), (p + "mlp.fc1.bias", (I,)),
+                 (p + "mlp.fc2.weight", (C_, I)), (p + "mlp.fc2.bias", (C_,)),
+                 (p + "layer_norm2.weight", (C_,)), (p + "layer_norm2.bias", (C_,))]
+    spec += [("text_model.final_layer_norm.weight", (C_,)), ("text_model.final_layer_norm.bias", (C_,))]
+    return spec
+
+
+def final_layer_norm(x, weight, bias, eps):
+    """LayerNorm over the last dim on the device (csrc/text.hip text_final_kernel), output in x's dtype"""
+    if not x.is_cuda:
+        raise RuntimeError("final_layer_norm: the tensor must live on the GPU; there is no CPU path")
+    xc = x.contiguous()
+    Cn = xc.shape[-1]
+    y = torch.empty_like(xc)
+    g = weight.detach().to(device=xc.device, dtype=torch.float32).contiguous()
+    b = bias.detach().to(device=xc.device, dtype=torch.float32).contiguous()
+    L.check(L.lib().ctrl_op_text_final_ln(L.ptr(xc), L.dtype_code(xc.dtype), xc.numel() // Cn, Cn, L.ptr(g), L.ptr(b), float(eps),
+                                          L.ptr(y), L.dtype_code(y.dtype), None, 0, 0, None, L.cur_stream()))
+    return y
+
+
+class _FinalLayerNorm(nn.Module):
+    """`text_model.final_layer_norm`: holds the weight / bias and applies them to a tensor (encode_controlnet_prompt's clip_skip
+    path calls it on a hidden state, model/ctrl_helper.py:382)"""
+
+    def __init__(self, eps):
+        super().__init__()
+        self.eps = eps
+
+    def forward(self, x):
+        return final_layer_norm(x, self.weight, self.bias, self.eps)
+
+
+class CLIPTextModel(ParamTreeModule):
+    def __init__(self, vocab_size=49408, hidden_size=512, intermediate_size=2048, projection_dim=512, num_hidden_layers=12,
+                 num_attention_heads=8, max_position_embeddings=77, hidden_act="quick_gelu", layer_norm_eps=1e-5,
+                 attention_dropout=0.0, initializer_range=0.02, initializer_factor=1.0, pad_token_id=1, bos_token_id=49406,
+                 eos_token_id=49407, **unused):
+        super().__init__()
+        self.config = Config({k: v for k, v in locals().items() if k not in ("self", "__class__", "unused")})
+        unsupported = []
+        if hidden_act != "quick_gelu":
+            unsupported.append("hidden_act %r (quick_gelu only)" % (hidden_act,))
+        if num_attention_heads < 1 or hidden_size != 64 * num_attention_heads:
+            unsupported.append("head_dim %s (64 only)" % (hidden_size / max(num_attention_heads, 1)))
+        if max_position_embeddings > 77:
+            unsupported.append("max_position_embeddings %d (<= 77)" % max_position_embeddings)
+        if hidden_size > 1024 or intermediate_size % 64:
+            unsupported.append("hidden_size > 1024 or intermediate_size not a multiple of 64")
+        if unsupported:
+            raise ValueError("CLIPTextModel (libctrlhip): unsupported configuration: " + ", ".join(unsupported))
+        cfg = L.TextEncoderConfig()
+        cfg.vocab_size, cfg.hidden_size, cfg.intermediate_size = vocab_size, hidden_size, intermediate_size
+        cfg.num_hidden_layers, cfg.num_attention_heads = num_hidden_layers, num_attention_heads
+        cfg.max_position_embeddings, cfg.eos_token_id, cfg.layer_norm_eps = max_position_embeddings, eos_token_id, layer_norm_eps
+        self._cfg = cfg
+        self.add_module("text_model", nn.Module())
+        self.text_model.add_module("final_layer_norm", _FinalLayerNorm(layer_norm_eps))
+        self._register_spec(text_encoder_spec(vocab_size, hidden_size, intermediate_size, num_hidden_layers, max_position_embeddings),
+                            dtype=torch.float32)
+
+    def config_dict(self):
+        return dict(self.config, architectures=["CLIPTextModel"], model_type="clip_text_model")
+
+    def load_state_dict(self, state_dict, strict=True, **k):
+        """accepts the transformers 4.x keys (`text_model.` prefix, SD-1.5's checkpoints) and the 5.x keys (no prefix); the
+        non-persistent `position_ids` buffer some checkpoints carry is dropped"""
+        sd = {}
+        for key, v in state_dict.items():
+            if key.endswith("embeddings.position_ids"):
+                continue
+            sd[key if key.startswith("text_model.") else "text_model." + key] = v
+        return super().load_state_dict(sd, strict=strict, **k)
+
+    def _destroy(self, plan):
+        L.lib().ctrl_text_encoder_destroy(plan)
+
+    def _ensure_plan(self):
+        if self._plan is None:
+            refs, n, keep = self._tensor_refs()
+            h = C.c_void_p()
+            L.check(L.lib().ctrl_text_encoder_create(C.byref(self._cfg), refs, n, L.cur_stream(), C.byref(h)))
+            self._plan = h
+        return self._plan
+
+    def forward(self, input_ids, attention_mask=None, position_ids=None, output_attentions=None, output_hidden_states=False,
+                return_dict=True):
+        if attention_mask is not None:
+            raise ValueError("CLIPTextModel (libctrlhip): attention_mask is not supported (the reference passes None, "
+                             "model/ctrl_helper.py:362)")
+        if position_ids is not None or output_attentions:
+            raise ValueError("CLIPTextModel (libctrlhip): position_ids / output_attentions are not supported")
+        dev = self.device
+        if not dev.type == "cuda":
+            raise RuntimeError("parameters must live on the GPU before the first forward (call .to('cuda')); there is no CPU path")
+        ids = input_ids
+        if ids.dim() == 1:
+            ids = ids[None]
+        if ids.dim() != 2 or ids.is_floating_point():
+            raise ValueError("input_ids must be an integer tensor [batch, tokens]")
+        N, Lt = ids.shape
+        if Lt < 1 or Lt > self.config.max_position_embeddings:
+            raise ValueError("input_ids: %d tokens (1 .. %d)" % (Lt, self.config.max_position_embeddings))
+        on_host = not ids.is_cuda
+        if on_host and ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.config.vocab_size):
+            raise ValueError("input_ids hold ids outside the vocabulary [0, %d)" % self.config.vocab_size)
+        ids = ids.to(device=dev, dtype=torch.int64).contiguous()
+        dt = self.dtype
+        Cn = self.config.hidden_size
+        last = torch.empty((N, Lt, Cn), dtype=dt, device=dev)
+        pooled = torch.empty((N, Cn), dtype=dt, device=dev)
+        hid = torch.empty((self.config.num_hidden_layers + 1, N, Lt, Cn), dtype=dt, device=dev) if output_hidden_states else None
+        with torch.cuda.device(dev):
+            plan = self._ensure_plan()
+            L.check(L.lib().ctrl_text_encoder_forward(plan, L.ptr(ids), N, Lt, L.ptr(last), L.ptr(pooled), L.ptr(hid),
+                                                      L.dtype_code(dt), L.cur_stream()))
+            if not on_host and not torch.cuda.is_current_stream_capturing():
+                if L.lib().ctrl_text_encoder_id_status(plan, 1) != 0:
+                    raise ValueError("input_ids hold ids outside the vocabulary [0, %d) (they were clamped)" % self.config.vocab_size)
+        L.raise_if_out_of_range("CLIPTextModel")
+        hs = tuple(hid.unbind(0)) if hid is not None else None
+        if not return_dict:
+            return (last, pooled) + ((hs,) if hs is not None else ())
+        return CLIPTextOutput(last, pooled, hs)
+
+
+def _check_ids_in_vocab(ids, text_encoder):
+    vocab = getattr(getattr(text_encoder, "config", None), "vocab_size", None)
+    if vocab is not None and ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= vocab):
+        raise ValueError("the tokenizer produced ids outside the text encoder's vocabulary [0, %d)" % vocab)
+
+
+@torch.no_grad()
+def encode_controlnet_prompt(tokenizer, text_encoder, prompt, device, num_images_per_prompt, do_classifier_free_guidance,
+                             negative_prompt=None, prompt_embeds=None, negative_prompt_embeds=None, lora_scale=None, clip_skip=None):
+    """ControlNetHelper.encode_controlnet_prompt (model/ctrl_helper.py:300-457) with the tokenizer and the text encoder passed in.
+    Returns (prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds).
+
+    The prompts and the negative prompts go through ONE encoder forward (with clip_skip, the prompt rows take final_layer_norm of
+    hidden state -(clip_skip + 1) and the negative rows the last hidden state, as in the reference's two calls).  Uses only the
+    encoder's module interface (`__call__`, `.dtype`, `.config`, `.text_model.final_layer_norm`).  Deviation: where the reference
+    raises UnboundLocalError -- no classifier-free guidance, or `prompt_embeds` / `negative_prompt_embeds` given -- the values it
+    never assigns are returned as None.  `lora_scale` is accepted and ignored, as in the reference."""
+    del lora_scale
+    if prompt is not None and isinstance(prompt, str):
+        batch_size = 1
+    elif prompt is not None and isinstance(prompt, list):
+        batch_size = len(prompt)
+    else:
+        batch_size = prompt_embeds.shape[0]
+
+    # the negative tokens (model/ctrl_helper.py:396-416), checked before anything runs
+    uncond_tokens = None
+    if do_classifier_free_guidance and negative_prompt_embeds is None:
+        if negative_prompt is None:
+            uncond_tokens = [""] * batch_size
+        elif prompt is not None and type(prompt) is not type(negative_prompt):
+            raise TypeError("`negative_prompt` should be the same type to `prompt`, but got %s != %s." % (type(negative_prompt), type(prompt)))
+        elif isinstance(negative_prompt, str):
+            uncond_tokens = [negative_prompt]
+        elif batch_size != len(negative_prompt):
+            raise ValueError("`negative_prompt`: %s has batch size %d, but `prompt`: %s has batch size %d. Please make sure that passed "
+                             "`negative_prompt` matches the batch size of `prompt`." % (negative_prompt, len(negative_prompt), prompt, batch_size))
+        else:
+            uncond_tokens = negative_prompt
+
+    def tokenize(texts, max_length):
+        ids = tokenizer(texts, padding="max_length", max_length=max_length, truncation=True, return_tensors="pt").input_ids
+        _check_ids_in_vocab(ids, text_encoder)
+        return ids
+
+    pooled_prompt_embeds = negative_pooled_prompt_embeds = None
+    neg_out = None
+    if prompt_embeds is None:
+        ids = tokenize(prompt, tokenizer.model_max_length)
+        n_pos = ids.shape[0]
+        if uncond_tokens is not None:
+            uids = tokenize(uncond_tokens, ids.shape[1])
+            ids = torch.cat([ids, uids], 0)
+        out = text_encoder(ids.to(device), attention_mask=None, output_hidden_states=clip_skip is not None)
+        if clip_skip is None:
+            prompt_embeds = out[0][:n_pos]
+        else:
+            prompt_embeds = text_encoder.text_model.final_layer_norm(out[-1][-(clip_skip + 1)][:n_pos])
+        pooled_prompt_embeds = out[1][:n_pos]
+        if uncond_tokens is not None:
+            neg_out = (out[0][n_pos:], out[1][n_pos:])
+
+    prompt_embeds_dtype = text_encoder.dtype if text_encoder is not None else prompt_embeds.dtype
+    prompt_embeds = prompt_embeds.to(dtype=prompt_embeds_dtype, device=device)
+    bs_embed, seq_len, _ = prompt_embeds.shape
+    prompt_embeds = prompt_embeds.repeat(1, num_images_per_prompt, 1).view(bs_embed * num_images_per_prompt, seq_len, -1)
+
+    if uncond_tokens is not None and neg_out is None:          # prompt_embeds were given: the negatives alone
+        uids = tokenize(uncond_tokens, seq_len)
+        o = text_encoder(uids.to(device), attention_mask=None)
+        neg_out = (o[0], o[1])
+    if neg_out is not None:
+        negative_prompt_embeds, negative_pooled_prompt_embeds = neg_out
+
+    if pooled_prompt_embeds is not None:
+        pooled_prompt_embeds = pooled_prompt_embeds.repeat(1, num_images_per_prompt).view(bs_embed * num_images_per_prompt, -1)
+
+    if do_classifier_free_guidance:
+        seq_len = negative_prompt_embeds.shape[1]
+        negative_prompt_embeds = negative_prompt_embeds.to(dtype=prompt_embeds_dtype, device=device)
+        negative_prompt_embeds = negative_prompt_embeds.repeat(1, num_images_per_prompt, 1).view(batch_size * num_images_per_prompt, seq_len, -1)
+        if negative_pooled_prompt_embeds is not None:
+            negative_pooled_prompt_embeds = negative_pooled_prompt_embeds.repeat(1, num_images_per_prompt).view(bs_embed * num_images_per_prompt, -1)
+
+    return prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds

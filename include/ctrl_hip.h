@@ -16,6 +16,8 @@
  *                             i2vgen_xl_controlnet_adapter_pipeline.py:1000-1022 (and train.py:1262-1276)
  *   ctrl_avgpool_nchw         replaces F.adaptive_avg_pool2d(latents,(64,64))  sdxl/pipelines/
  *                             sdxl_controlnet_adapter_pipeline.py:1306-1309
+ *   ctrl_text_encoder_forward replaces the CLIPTextModel call of ControlNetHelper.encode_controlnet_prompt
+ *                             model/ctrl_helper.py:300-457 (SD-1.5's CLIP ViT-L/14 text tower)
  * Op-level entry points (ctrl_op_*) expose the individual kernels for parity tests and micro-benchmarks.
  */
 #ifndef CTRL_HIP_H
@@ -79,7 +81,7 @@ typedef struct ctrl_igemm_desc {
     float scale;
     int32_t geglu;      /* weights packed in interleaved (hidden,gate) 16-column blocks; out width Nout/2 */
     int32_t nseg;
-    int32_t act;        /* 0 none, 1 SiLU applied after bias/rowvec (before residual) */
+    int32_t act;        /* 0 none, 1 SiLU, 2 quick_gelu x*sigmoid(1.702x) (CLIP's MLP); applied after bias/rowvec (before residual) */
     int32_t res_f32;    /* residual is fp32 (the fp32 residual stream) */
     int32_t a_split;    /* split operand: A rows hold [hi | lo] fp16 halves of an fp32 operand along Cin (lo = fp16(x - hi)), so the
                            product is exact in A to ~2^-22 at twice the MFMA work (the ControlNet's convolutions).
@@ -447,6 +449,48 @@ int ctrl_step_forward(ctrl_controlnet* cn, ctrl_adapter* ad,
                       int num_frames, const float* ad_timesteps, int ad_t_count,
                       const void* ad_encoder_hidden_states, int ad_ehs_dtype, int ad_ehs_batch, int ad_Lk,
                       int use_mid, void* const* outs, int out_dtype, const int32_t* frame_pos, int N_out, void* stream);
+
+/* ---- CLIP text encoder (transformers CLIPTextModel, the SD-1.5 text_encoder; model/ctrl_helper.py:34-41,300-457) ----
+ * Pre-LN transformer: x = tok_emb[ids] + pos_emb[:L]; per layer x += out_proj(causal_attn(qkv(LN1(x)))), x += fc2(quick_gelu(fc1(LN2(x))));
+ * last_hidden_state = final_layer_norm(x); pooled = last_hidden_state[argmax(ids)] when eos_token_id == 2 (the legacy rule of
+ * SD-1.5's config), else at the first position of eos_token_id.  Residual stream fp32, GEMM operands fp16, head_dim 64, L <= 77
+ * (<= 128). */
+typedef struct ctrl_text_encoder_config {
+    int32_t vocab_size;                /* 49408 */
+    int32_t hidden_size;               /* 768 (<= 1024, multiple of 64) */
+    int32_t intermediate_size;         /* 3072 (multiple of 64) */
+    int32_t num_hidden_layers;         /* 12 */
+    int32_t num_attention_heads;       /* 12 (hidden_size / heads must be 64) */
+    int32_t max_position_embeddings;   /* 77 (<= 128) */
+    int32_t eos_token_id;              /* 2 = the argmax rule */
+    float layer_norm_eps;              /* 1e-5 */
+} ctrl_text_encoder_config;
+typedef struct ctrl_text_encoder ctrl_text_encoder;   /* opaque */
+/* weights: the state-dict tensors under their transformers 4.x keys (text_model.embeddings.token_embedding.weight, ...,
+ * text_model.encoder.layers.{i}.self_attn.q_proj.weight, ..., text_model.final_layer_norm.bias), any dtype, device memory;
+ * packed into plan-owned memory (GEMM weights fp16, the embedding tables / norms / biases fp32) -- synchronises `stream` once */
+int ctrl_text_encoder_create(const ctrl_text_encoder_config* cfg, const ctrl_tensor_ref* tensors, int n_tensors, void* stream,
+                             ctrl_text_encoder** out);
+void ctrl_text_encoder_destroy(ctrl_text_encoder* h);
+/* input_ids int64 device [N][L] (1 <= L <= max_position_embeddings); outputs in out_dtype (NULL = not written):
+ * last_hidden [N][L][hidden], pooled [N][hidden], hidden_states [num_hidden_layers + 1][N][L][hidden] (the embedding output and the
+ * stream after every layer, before the final LayerNorm: transformers' output_hidden_states).  Never synchronises; capturable.
+ * Every prompt is computed by the same instruction sequence whatever N: its rows are bit-identical alone or inside a batch.
+ * An id outside [0, vocab_size) is clamped and raises the plan's flag word (ctrl_text_encoder_id_status). */
+int ctrl_text_encoder_forward(ctrl_text_encoder* h, const int64_t* input_ids, int N, int L, void* last_hidden, void* pooled,
+                              void* hidden_states, int out_dtype, void* stream);
+/* 1 when a forward since the last reset met an id outside the vocabulary; reset = 1 clears the flag.  Synchronises the device. */
+int ctrl_text_encoder_id_status(ctrl_text_encoder* h, int reset);
+/* op level (csrc/text.hip).  embed: x fp32 [N*L][C] = tok[clamp(ids)] + pos[l], y fp16 = LayerNorm(x; gamma, beta); tok / pos fp32;
+ * bad (device, optional) set to 1 by an id outside [0, V).  attn: causal softmax(q k^T * scale) v per (prompt, head) over L <= 128
+ * tokens, head_dim 64, qkv fp16 [N*L][ld] (q of head h at column h*64, k at heads*64 + h*64, v at 2*heads*64 + h*64), out fp16
+ * [N*L][ldo].  final_ln: y [rows][C] (y_dtype) = LayerNorm(x [rows][C], x_dtype); with ids (int64 [rows / L][L]) and pooled, the
+ * prompt's pooled row (rule of eos_token_id above) goes to pooled [rows / L][C] as well. */
+int ctrl_op_text_embed(const int64_t* ids, const float* tok, const float* pos, int V, int N, int L, int C, float* x,
+                       const float* gamma, const float* beta, float eps, void* y, int32_t* bad, void* stream);
+int ctrl_op_text_attn(const void* qkv, int64_t ld, void* out, int64_t ldo, int N, int L, int heads, float scale, void* stream);
+int ctrl_op_text_final_ln(const void* x, int x_dtype, int rows, int C, const float* gamma, const float* beta, float eps,
+                          void* y, int y_dtype, const int64_t* ids, int L, int eos_token_id, void* pooled, void* stream);
 
 /* ---- Router (model/ctrl_router.py) ---- */
 /* weights_out fp32 device [num_routers + (has_mid?1:0)][E]; wg fp32 device same shape (Linear(1,E).weight[:,0]
