@@ -7,3 +7,4 @@ from .ctrl_router import ControlNetRouter  # noqa: F401
 from .fused import controlled_step  # noqa: F401
 from .image_prep import prepare_images  # noqa: F401
 from .text_encoder import CLIPTextModel, CLIPTextOutput, encode_controlnet_prompt  # noqa: F401
+from .text_encoder import CLIPTextModelWithProjection, CLIPTextModelOutput, encode_sdxl_prompt  # noqa: F401

@@ -80,6 +80,10 @@ class TextEncoderConfig(C.Structure):
                 ("eos_token_id", C.c_int32), ("layer_norm_eps", C.c_float)]
 
 
+class TextEncoderExt(C.Structure):
+    _fields_ = [("hidden_act", C.c_int32), ("projection_dim", C.c_int32), ("gemm_form", C.c_int32), ("reserved", C.c_int32)]
+
+
 CB_GATHER = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p)
 CB_REDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)
 CB_HALO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p)
@@ -111,6 +115,7 @@ EXPORTS = [
     "ctrl_router_weights", "ctrl_router_merge", "ctrl_prepare_images",
     "ctrl_text_encoder_create", "ctrl_text_encoder_destroy", "ctrl_text_encoder_forward", "ctrl_text_encoder_id_status",
     "ctrl_op_text_embed", "ctrl_op_text_attn", "ctrl_op_text_final_ln",
+    "ctrl_text_encoder_create_ext", "ctrl_text_encoder_forward_ext", "ctrl_text_gemm_ws_bytes", "ctrl_op_text_gemm",
 ]
 
 _lib = None
@@ -145,6 +150,12 @@ def lib():
                                                C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _lib.ctrl_text_encoder_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_int, C.c_void_p]
+        _lib.ctrl_text_encoder_forward_ext.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        _lib.ctrl_text_gemm_ws_bytes.restype = C.c_int64
+        _lib.ctrl_text_gemm_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+        _lib.ctrl_op_text_gemm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                           C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
         _lib.ctrl_rccl_comm_destroy.restype = None
         _lib.ctrl_rccl_comm_destroy.argtypes = [C.c_void_p]
         _lib.ctrl_rccl_comm_bytes_sent.restype = C.c_int64

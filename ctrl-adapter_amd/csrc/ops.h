@@ -114,6 +114,20 @@ int op_text_attn(const half_t* qkv, long ld, half_t* out, long ldo, int N, int L
 int op_text_final(const void* x, int x_dt, int rows, int C, const float* gamma, const float* beta, float eps, void* y, int y_dt,
                   const int64_t* ids, int L, int eos, void* pooled, hipStream_t s);
 int op_text_store(const float* x, void* y, int y_dt, size_t n, hipStream_t s);
+// op_text_final with C up to 2048 (multiples of 64 above 1024) and the pooled row also in fp32 (pooled32 [N][C], may be null)
+int op_text_final_ext(const void* x, int x_dt, int rows, int C, const float* gamma, const float* beta, float eps, void* y, int y_dt,
+                      const int64_t* ids, int L, int eos, void* pooled, float* pooled32, hipStream_t s);
+// Batch-invariant few-row GEMM (text_gemm.hip): y[M][N] (y_dt) = act(x[M][K] W^T + b) (+ res fp32 [M][N]); act 0 / 2 quick_gelu /
+// 3 exact gelu; N % 16 == 0, K % 32 == 0; ws >= text_gemm_ws_bytes(M, N, K) (fp32 split-K partials, reduced in a fixed order)
+int text_gemm_splits(int N, int K);
+size_t text_gemm_ws_bytes(int M, int N, int K);
+int op_text_gemm(const half_t* x, const half_t* W, const float* bias, int M, int N, int K, int act, const float* res, void* y, int y_dt,
+                 float* ws, size_t ws_bytes, hipStream_t s);
+// y = act(sum of `splits` fp32 planes [M][N] + b) (+ res): the reduction of op_text_gemm (also the unfused activation of a pinned GEMM)
+int op_text_gemm_finish(const float* ws, int splits, int M, int N, const float* bias, int act, const float* res, long ldres, void* y,
+                        int y_dt, long ldy, hipStream_t s);
+// text_embeds[n] = pooled32[n] . Wp^T in fp32 (Wp fp32 [P][C], no bias), out [N][P] in out_dt
+int op_text_proj(const float* pooled32, const float* Wp, int N, int C, int P, void* out, int out_dt, hipStream_t s);
 
 // temporal attention over the frame axis: tokens X [(b*F+f)*HW + p][...]; seq = F (<= 32)
 typedef ctrl_tattn_desc TAttnArgs;

@@ -4,7 +4,10 @@
 //   LN1(next) | final LayerNorm + pooled row.
 // Residual stream fp32 (two ping-pong buffers), GEMM operands fp16.  Every GEMM runs in the one pinned form (op_igemm_pinned) and every
 // other kernel computes rows or (prompt, head) pairs on their own, so a prompt's outputs are bit-identical whatever the batch it is in.
+// The ext plan (ctrl_text_encoder_create_ext: SDXL's OpenCLIP bigG text_encoder_2) adds exact gelu, hidden sizes up to 2048, the
+// fp32 text projection of the pooled row and the few-row GEMM of text_gemm.hip (gemm_form 1), equally batch-invariant.
 #include "plan_common.h"
+#include <algorithm>
 #include <cmath>
 
 namespace {
@@ -16,6 +19,8 @@ struct TextLayer {
 
 struct TextEncoder : PlanBase {
     ctrl_text_encoder_config cfg{};
+    ctrl_text_encoder_ext ext{};     // zeros: quick_gelu, no projection, the pinned GEMM (what ctrl_text_encoder_create builds)
+    float* proj = nullptr;           // text_projection.weight fp32 [projection_dim][hidden]
     Packer* pk = nullptr;
     float* tok = nullptr;
     float* pos = nullptr;
@@ -29,10 +34,11 @@ struct TextEncoder : PlanBase {
     }
 };
 
-int validate(const ctrl_text_encoder_config& c) {
+int validate(const ctrl_text_encoder_config& c, int max_hidden) {
     CTRL_CHECK(c.vocab_size >= 1 && c.num_hidden_layers >= 1, "text encoder: vocab_size and num_hidden_layers must be positive");
-    CTRL_CHECK(c.hidden_size >= 64 && c.hidden_size <= 1024 && c.hidden_size % 64 == 0,
-               "text encoder: hidden_size must be a multiple of 64 up to 1024");
+    CTRL_CHECK(c.hidden_size >= 64 && c.hidden_size <= max_hidden && c.hidden_size % 64 == 0,
+               max_hidden == 1024 ? "text encoder: hidden_size must be a multiple of 64 up to 1024"
+                                  : "text encoder: hidden_size must be a multiple of 64 up to 2048");
     CTRL_CHECK(c.num_attention_heads >= 1 && c.hidden_size == 64 * c.num_attention_heads, "text encoder: head_dim must be 64");
     CTRL_CHECK(c.intermediate_size >= 64 && c.intermediate_size % 64 == 0, "text encoder: intermediate_size must be a multiple of 64");
     CTRL_CHECK(c.max_position_embeddings >= 1 && c.max_position_embeddings <= 128, "text encoder: max_position_embeddings must be <= 128");
@@ -57,6 +63,15 @@ int build_text(ParamSink& ps, TextEncoder& t) {
         TRY(ps.linear(pre + "mlp.fc2", C, I, true, false, &l.fc2));
     }
     TRY(ps.norm("text_model.final_layer_norm", C, &t.final_ln));
+    if (t.ext.projection_dim > 0) TRY(ps.raw_f32("text_projection.weight", {t.ext.projection_dim, C}, &t.proj));
+    return 0;
+}
+
+int validate_ext(const ctrl_text_encoder_ext& e) {
+    CTRL_CHECK(e.hidden_act == 0 || e.hidden_act == 1, "text encoder: hidden_act must be 0 (quick_gelu) or 1 (gelu)");
+    CTRL_CHECK(e.projection_dim >= 0 && e.projection_dim <= 65536, "text encoder: projection_dim must be 0 .. 65536");
+    CTRL_CHECK(e.gemm_form == 0 || e.gemm_form == 1, "text encoder: gemm_form must be 0 (pinned) or 1 (few-row GEMM)");
+    CTRL_CHECK(e.reserved == 0, "text encoder: ctrl_text_encoder_ext.reserved must be 0");
     return 0;
 }
 
@@ -73,18 +88,48 @@ int linear(const Lin& l, const half_t* x, void* y, int y_dt, int M, const float*
 
 size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-int forward(TextEncoder& t, const int64_t* ids, int N, int L, void* last, void* pooled, void* hidden, int odt, hipStream_t s) {
+// scratch a linear of the plan's form needs besides its output: the split-K partials (form 1) or the fp32 pre-activation of an
+// exact-gelu fc1 on the pinned form (form 0: the shared implicit-GEMM epilogue has no erf; the fp32 pass applies it in the same order,
+// bias -> act -> residual)
+struct LinScratch { float* p = nullptr; size_t bytes = 0; };
+
+int run_linear(const TextEncoder& t, const Lin& l, const half_t* x, void* y, int y_dt, int M, const float* res, int act, const LinScratch& ws,
+               hipStream_t s) {
+    if (t.ext.gemm_form == 1) return op_text_gemm(x, l.w, l.b, M, l.N, l.K, act, res, y, y_dt, ws.p, ws.bytes, s);
+    if (act != 3) return linear(l, x, y, y_dt, M, res, act, s);
+    TRY(linear(l, x, ws.p, DT_F32, M, nullptr, 0, s));
+    return op_text_gemm_finish(ws.p, 1, M, l.N, nullptr, 3, res, l.N, y, y_dt, l.N, s);
+}
+
+size_t lin_scratch_bytes(const TextEncoder& t, int M) {
     const ctrl_text_encoder_config& c = t.cfg;
-    CTRL_CHECK(ids != nullptr && (last || pooled || hidden), "text encoder: ids and at least one output are required");
+    const size_t C = c.hidden_size, I = c.intermediate_size;
+    if (t.ext.gemm_form == 1)
+        return std::max(std::max(text_gemm_ws_bytes(M, 3 * C, C), text_gemm_ws_bytes(M, C, C)),
+                        std::max(text_gemm_ws_bytes(M, I, C), text_gemm_ws_bytes(M, C, I)));
+    return t.ext.hidden_act == 1 ? (size_t)M * I * 4 : 0;
+}
+
+// hidden_index -1: every state into hidden [layers + 1][N][L][C]; k >= 0: state k alone into hidden [N][L][C], and with no
+// last / pooled / embeds requested the layers after k are not run
+int forward(TextEncoder& t, const int64_t* ids, int N, int L, void* last, void* pooled, void* embeds, void* hidden, int hidden_index, int odt,
+            hipStream_t s) {
+    const ctrl_text_encoder_config& c = t.cfg;
+    CTRL_CHECK(ids != nullptr && (last || pooled || embeds || hidden), "text encoder: ids and at least one output are required");
     CTRL_CHECK(N >= 1 && L >= 1 && L <= c.max_position_embeddings, "text encoder: need N >= 1 and 1 <= L <= max_position_embeddings");
     CTRL_CHECK(odt == DT_F32 || odt == DT_F16 || odt == DT_BF16, "text encoder: out_dtype must be fp32, fp16 or bf16");
     CTRL_CHECK((long)N * L <= (1L << 24), "text encoder: batch too large");
+    CTRL_CHECK(hidden_index >= -1 && hidden_index <= c.num_hidden_layers, "text encoder: hidden_index must be -1 .. num_hidden_layers");
+    CTRL_CHECK(!embeds || t.proj, "text encoder: text_embeds needs a plan with a text projection (projection_dim > 0)");
     const int C = c.hidden_size, I = c.intermediate_size, M = N * L;
     const float eps = c.layer_norm_eps;
+    const bool tail = last || pooled || embeds;
+    const int layers = (!tail && hidden_index >= 0) ? hidden_index : c.num_hidden_layers;
     // workspace: two fp32 stream buffers, the fp16 LayerNorm output, Q | K | V, the attention output, the MLP hidden activation
+    // (+ the linears' scratch and the fp32 pooled rows of the projection)
     const size_t b_x = al256((size_t)M * C * 4), b_h = al256((size_t)M * C * 2), b_qkv = al256((size_t)M * 3 * C * 2),
-                 b_ff = al256((size_t)M * I * 2);
-    const size_t need = 2 * b_x + 2 * b_h + b_qkv + b_ff;
+                 b_ff = al256((size_t)M * I * 2), b_lin = al256(lin_scratch_bytes(t, M)), b_p32 = t.proj ? al256((size_t)N * C * 4) : 0;
+    const size_t need = 2 * b_x + 2 * b_h + b_qkv + b_ff + b_lin + b_p32;
     bool capturing = false;
     TRY(t.enter(s, &capturing));
     CTRL_CHECK(!capturing || need <= t.ar.cap, "text encoder: the first forward of a larger batch allocates its workspace and cannot run "
@@ -96,30 +141,56 @@ int forward(TextEncoder& t, const int64_t* ids, int N, int L, void* last, void* 
     half_t* h16 = (half_t*)p; p += b_h;
     half_t* ao = (half_t*)p; p += b_h;
     half_t* qkv = (half_t*)p; p += b_qkv;
-    half_t* ff = (half_t*)p;
+    half_t* ff = (half_t*)p; p += b_ff;
+    LinScratch lws;
+    lws.p = b_lin ? (float*)p : nullptr; lws.bytes = b_lin; p += b_lin;
+    float* p32 = b_p32 ? (float*)p : nullptr;
     const size_t esz = odt == DT_F32 ? 4 : 2;
     auto snap = [&](int k, const float* x) -> int {     // hidden_states[k] = the stream after k layers
-        if (!hidden) return 0;
-        return op_text_store(x, (char*)hidden + (size_t)k * M * C * esz, odt, (size_t)M * C, s);
+        if (!hidden || (hidden_index >= 0 && k != hidden_index)) return 0;
+        const size_t slot = hidden_index >= 0 ? 0 : (size_t)k;
+        return op_text_store(x, (char*)hidden + slot * M * C * esz, odt, (size_t)M * C, s);
     };
+    const int fc1_act = t.ext.hidden_act == 1 ? 3 : 2;
     TRY(op_text_embed(ids, t.tok, t.pos, c.vocab_size, N, L, C, xa, t.layers[0].ln1.g, t.layers[0].ln1.b, eps, h16, t.bad, s));
     TRY(snap(0, xa));
     const float scale = 1.0f / std::sqrt(64.0f);
-    for (int i = 0; i < c.num_hidden_layers; ++i) {
+    for (int i = 0; i < layers; ++i) {
         const TextLayer& l = t.layers[i];
-        TRY(linear(l.qkv, h16, qkv, DT_F16, M, nullptr, 0, s));
+        TRY(run_linear(t, l.qkv, h16, qkv, DT_F16, M, nullptr, 0, lws, s));
         TRY(op_text_attn(qkv, 3L * C, ao, C, N, L, c.num_attention_heads, scale, s));
-        TRY(linear(l.out, ao, xb, DT_F32, M, xa, 0, s));
+        TRY(run_linear(t, l.out, ao, xb, DT_F32, M, xa, 0, lws, s));
         TRY(op_layernorm(xb, DT_F32, C, l.ln2.g, l.ln2.b, h16, C, M, C, eps, s));
-        TRY(linear(l.fc1, h16, ff, DT_F16, M, nullptr, 2, s));
-        TRY(linear(l.fc2, ff, xa, DT_F32, M, xb, 0, s));
+        TRY(run_linear(t, l.fc1, h16, ff, DT_F16, M, nullptr, fc1_act, lws, s));
+        TRY(run_linear(t, l.fc2, ff, xa, DT_F32, M, xb, 0, lws, s));
         TRY(snap(i + 1, xa));
-        if (i + 1 < c.num_hidden_layers)
+        if (i + 1 < layers)
             TRY(op_layernorm(xa, DT_F32, C, t.layers[i + 1].ln1.g, t.layers[i + 1].ln1.b, h16, C, M, C, eps, s));
     }
-    if (last || pooled)
-        TRY(op_text_final(xa, DT_F32, M, C, t.final_ln.g, t.final_ln.b, eps, last, odt, ids, L, c.eos_token_id, pooled, s));
+    if (last || pooled || embeds)
+        TRY(op_text_final_ext(xa, DT_F32, M, C, t.final_ln.g, t.final_ln.b, eps, last, odt, ids, L, c.eos_token_id, pooled,
+                              embeds ? p32 : nullptr, s));
+    if (embeds) TRY(op_text_proj(p32, t.proj, N, C, t.ext.projection_dim, embeds, odt, s));
     return t.leave(s, capturing);
+}
+
+int create(const ctrl_text_encoder_config* cfg, const ctrl_text_encoder_ext* ext, const ctrl_tensor_ref* tensors, int n_tensors, void* stream,
+           ctrl_text_encoder** out) {
+    TextEncoder* t = new TextEncoder();
+    t->cfg = *cfg;
+    if (ext) t->ext = *ext;
+    int rc = t->init_base(n_tensors ? tensors[0].data : nullptr);
+    DeviceGuard dg(t->device);
+    if (!rc) {
+        t->pk = new Packer(tensors, n_tensors, (hipStream_t)stream);
+        rc = build_text(*t->pk, *t);
+        if (!rc) rc = t->pk->finish();
+    }
+    if (!rc && hipMalloc((void**)&t->bad, sizeof(int)) != hipSuccess) { ctrl_set_error("text_encoder_create: hipMalloc failed"); rc = 1; }
+    if (!rc && hipMemset(t->bad, 0, sizeof(int)) != hipSuccess) { ctrl_set_error("text_encoder_create: hipMemset failed"); rc = 1; }
+    if (rc) { delete t; return rc; }
+    *out = (ctrl_text_encoder*)t;
+    return 0;
 }
 
 }  // namespace
@@ -132,21 +203,17 @@ int ctrl_text_encoder_create(const ctrl_text_encoder_config* cfg, const ctrl_ten
                              ctrl_text_encoder** out) {
     CTRL_CHECK(cfg && out && (tensors || n_tensors == 0), "text_encoder_create: null argument");
     *out = nullptr;
-    TRY(validate(*cfg));
-    TextEncoder* t = new TextEncoder();
-    t->cfg = *cfg;
-    int rc = t->init_base(n_tensors ? tensors[0].data : nullptr);
-    DeviceGuard dg(t->device);
-    if (!rc) {
-        t->pk = new Packer(tensors, n_tensors, S(stream));
-        rc = build_text(*t->pk, *t);
-        if (!rc) rc = t->pk->finish();
-    }
-    if (!rc && hipMalloc((void**)&t->bad, sizeof(int)) != hipSuccess) { ctrl_set_error("text_encoder_create: hipMalloc failed"); rc = 1; }
-    if (!rc && hipMemset(t->bad, 0, sizeof(int)) != hipSuccess) { ctrl_set_error("text_encoder_create: hipMemset failed"); rc = 1; }
-    if (rc) { delete t; return rc; }
-    *out = (ctrl_text_encoder*)t;
-    return 0;
+    TRY(validate(*cfg, 1024));
+    return create(cfg, nullptr, tensors, n_tensors, stream, out);
+}
+
+int ctrl_text_encoder_create_ext(const ctrl_text_encoder_config* cfg, const ctrl_text_encoder_ext* ext, const ctrl_tensor_ref* tensors,
+                                 int n_tensors, void* stream, ctrl_text_encoder** out) {
+    CTRL_CHECK(cfg && ext && out && (tensors || n_tensors == 0), "text_encoder_create_ext: null argument");
+    *out = nullptr;
+    TRY(validate(*cfg, 2048));
+    TRY(validate_ext(*ext));
+    return create(cfg, ext, tensors, n_tensors, stream, out);
 }
 
 void ctrl_text_encoder_destroy(ctrl_text_encoder* h) {
@@ -162,7 +229,15 @@ int ctrl_text_encoder_forward(ctrl_text_encoder* h, const int64_t* input_ids, in
     CTRL_CHECK(h != nullptr, "text_encoder_forward: null plan");
     TextEncoder* t = (TextEncoder*)h;
     DeviceGuard dg(t->device);
-    return forward(*t, input_ids, N, L, last_hidden, pooled, hidden_states, out_dtype, S(stream));
+    return forward(*t, input_ids, N, L, last_hidden, pooled, nullptr, hidden_states, -1, out_dtype, S(stream));
+}
+
+int ctrl_text_encoder_forward_ext(ctrl_text_encoder* h, const int64_t* input_ids, int N, int L, void* last_hidden, void* pooled,
+                                  void* text_embeds, void* hidden_states, int hidden_index, int out_dtype, void* stream) {
+    CTRL_CHECK(h != nullptr, "text_encoder_forward_ext: null plan");
+    TextEncoder* t = (TextEncoder*)h;
+    DeviceGuard dg(t->device);
+    return forward(*t, input_ids, N, L, last_hidden, pooled, text_embeds, hidden_states, hidden_index, out_dtype, S(stream));
 }
 
 int ctrl_text_encoder_id_status(ctrl_text_encoder* h, int reset) {
@@ -187,6 +262,17 @@ int ctrl_op_text_attn(const void* qkv, int64_t ld, void* out, int64_t ldo, int N
 int ctrl_op_text_final_ln(const void* x, int x_dtype, int rows, int C, const float* gamma, const float* beta, float eps,
                           void* y, int y_dtype, const int64_t* ids, int L, int eos_token_id, void* pooled, void* stream) {
     return op_text_final(x, x_dtype, rows, C, gamma, beta, eps, y, y_dtype, ids, L, eos_token_id, pooled, S(stream));
+}
+
+int64_t ctrl_text_gemm_ws_bytes(int M, int N, int K) {
+    if (M < 1 || N < 1 || K < 1) return 0;
+    return (int64_t)text_gemm_ws_bytes(M, N, K);
+}
+
+int ctrl_op_text_gemm(const void* x, const void* W, const float* bias, int M, int N, int K, int act, const float* res, void* y, int y_dtype,
+                      void* ws, int64_t ws_bytes, void* stream) {
+    CTRL_CHECK(ws_bytes >= 0, "text_gemm: ws_bytes must be >= 0");
+    return op_text_gemm((const half_t*)x, (const half_t*)W, bias, M, N, K, act, res, y, y_dtype, (float*)ws, (size_t)ws_bytes, S(stream));
 }
 
 }  // extern "C"

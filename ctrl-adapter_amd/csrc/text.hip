@@ -3,6 +3,8 @@
 //   text_attn_kernel       causal self-attention over L <= 128 tokens, head_dim 64, straight from the Q | K | V GEMM output
 //   text_final_kernel      final LayerNorm of every row into the output dtype + the pooled row (index chosen on the device)
 //   text_store_kernel      fp32 stream -> output dtype (the hidden_states snapshots)
+// The row kernels serve C <= 1024 (SD-1.5's 768); text_embed_ln_wide_kernel and text_final_ext_kernel<8> serve multiples of 64 up to
+// 2048 (OpenCLIP bigG's 1280), and text_final_ext_kernel also writes the fp32 pooled row the text projection reads (text_gemm.hip).
 // Every kernel computes a row (embedding, norms) or a (prompt, head, 16-query tile) (attention) on its own: a prompt's results do not
 // depend on the other prompts of the batch (the plan's batch invariance, plan_text.cpp).
 #include "ops.h"
@@ -12,7 +14,8 @@
 namespace {
 
 constexpr int kRowThreads = 256;
-constexpr int kRowPer = 4;           // C <= kRowThreads * kRowPer
+constexpr int kRowPer = 4;           // C <= kRowThreads * kRowPer (the SD-1.5 kernels)
+constexpr int kRowPerWide = 8;       // C <= 2048: the wider towers (OpenCLIP bigG, 1280) in their own instantiations
 
 // sum over the 256 threads of a row workgroup (4 waves), same value in every thread
 __device__ __forceinline__ float block_sum256(float v, float* red) {
@@ -24,33 +27,34 @@ __device__ __forceinline__ float block_sum256(float v, float* red) {
     return red[0] + red[1] + red[2] + red[3];
 }
 
-// LayerNorm of the kRowPer values a thread holds (columns threadIdx.x + i * 256 < C), two-pass statistics in fp32
-__device__ __forceinline__ void row_ln(float (&v)[kRowPer], int C, float eps, const float* g, const float* b, float* red) {
+// LayerNorm of the PER values a thread holds (columns threadIdx.x + i * 256 < C), two-pass statistics in fp32
+template <int PER>
+__device__ __forceinline__ void row_ln(float (&v)[PER], int C, float eps, const float* g, const float* b, float* red) {
     float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < kRowPer; ++i) s += v[i];
+    for (int i = 0; i < PER; ++i) s += v[i];
     const float mean = block_sum256(s, red) / (float)C;
     float q = 0.f;
 #pragma unroll
-    for (int i = 0; i < kRowPer; ++i) {
+    for (int i = 0; i < PER; ++i) {
         const int c = threadIdx.x + i * kRowThreads;
         const float d = c < C ? v[i] - mean : 0.f;
         q += d * d;
     }
     const float rstd = rsqrtf(block_sum256(q, red) / (float)C + eps);
 #pragma unroll
-    for (int i = 0; i < kRowPer; ++i) {
+    for (int i = 0; i < PER; ++i) {
         const int c = threadIdx.x + i * kRowThreads;
         if (c < C) v[i] = (v[i] - mean) * rstd * g[c] + b[c];
     }
 }
 
 // one workgroup per token row (prompt n, position l): x = tok[clamp(id)] + pos[l] (fp32 stream), y = LayerNorm(x) (fp16)
-__global__ __launch_bounds__(kRowThreads) void text_embed_ln_kernel(const int64_t* __restrict__ ids, const float* __restrict__ tok,
-                                                                    const float* __restrict__ pos, int V, int L, int C, float* __restrict__ x,
-                                                                    const float* __restrict__ g, const float* __restrict__ b, float eps,
-                                                                    half_t* __restrict__ y, int* __restrict__ bad) {
-    __shared__ float red[4];
+template <int PER>
+__device__ __forceinline__ void text_embed_ln_body(const int64_t* __restrict__ ids, const float* __restrict__ tok, const float* __restrict__ pos,
+                                                   int V, int L, int C, float* __restrict__ x, const float* __restrict__ g,
+                                                   const float* __restrict__ b, float eps, half_t* __restrict__ y, int* __restrict__ bad,
+                                                   float* red) {
     const int row = blockIdx.x;
     const int l = row % L;
     int64_t id = ids[row];
@@ -60,9 +64,9 @@ __global__ __launch_bounds__(kRowThreads) void text_embed_ln_kernel(const int64_
     }
     const float* te = tok + (size_t)id * C;
     const float* pe = pos + (size_t)l * C;
-    float v[kRowPer];
+    float v[PER];
 #pragma unroll
-    for (int i = 0; i < kRowPer; ++i) {
+    for (int i = 0; i < PER; ++i) {
         const int c = threadIdx.x + i * kRowThreads;
         v[i] = 0.f;
         if (c < C) {
@@ -72,10 +76,27 @@ __global__ __launch_bounds__(kRowThreads) void text_embed_ln_kernel(const int64_
     }
     row_ln(v, C, eps, g, b, red);
 #pragma unroll
-    for (int i = 0; i < kRowPer; ++i) {
+    for (int i = 0; i < PER; ++i) {
         const int c = threadIdx.x + i * kRowThreads;
         if (c < C) y[(size_t)row * C + c] = (half_t)v[i];
     }
+}
+
+__global__ __launch_bounds__(kRowThreads) void text_embed_ln_kernel(const int64_t* __restrict__ ids, const float* __restrict__ tok,
+                                                                    const float* __restrict__ pos, int V, int L, int C, float* __restrict__ x,
+                                                                    const float* __restrict__ g, const float* __restrict__ b, float eps,
+                                                                    half_t* __restrict__ y, int* __restrict__ bad) {
+    __shared__ float red[4];
+    text_embed_ln_body<kRowPer>(ids, tok, pos, V, L, C, x, g, b, eps, y, bad, red);
+}
+
+// 1024 < C <= 2048
+__global__ __launch_bounds__(kRowThreads) void text_embed_ln_wide_kernel(const int64_t* __restrict__ ids, const float* __restrict__ tok,
+                                                                         const float* __restrict__ pos, int V, int L, int C, float* __restrict__ x,
+                                                                         const float* __restrict__ g, const float* __restrict__ b, float eps,
+                                                                         half_t* __restrict__ y, int* __restrict__ bad) {
+    __shared__ float red[4];
+    text_embed_ln_body<kRowPerWide>(ids, tok, pos, V, L, C, x, g, b, eps, y, bad, red);
 }
 
 // pooled position of prompt n (transformers CLIPTextTransformer): eos_id == 2 (the legacy configs SD-1.5 carries) -> the first
@@ -104,6 +125,44 @@ __device__ int pooled_index(const int64_t* ids, int L, int eos, int* red_i) {
 }
 
 // one workgroup per row: y[row] = LayerNorm(x[row]) in y_dt; with ids, the prompt's pooled row is also written to pooled[row / L]
+// (in y_dt) and, with pooled32, in fp32 to pooled32[row / L] (the text projection's operand)
+template <int PER>
+__device__ __forceinline__ void text_final_body(const void* __restrict__ x, int x_dt, int C, const float* __restrict__ g,
+                                                const float* __restrict__ b, float eps, void* __restrict__ y, int y_dt,
+                                                const int64_t* __restrict__ ids, int L, int eos, void* __restrict__ pooled,
+                                                float* __restrict__ pooled32, float* red, int* red_i) {
+    const int row = blockIdx.x;
+    float v[PER];
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        const int c = threadIdx.x + i * kRowThreads;
+        v[i] = c < C ? load_as_f32(x, (size_t)row * C + c, x_dt) : 0.f;
+    }
+    row_ln(v, C, eps, g, b, red);
+    if (y) {
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+            const int c = threadIdx.x + i * kRowThreads;
+            if (c < C) store_from_f32(y, (size_t)row * C + c, y_dt, v[i]);
+        }
+    }
+    if (ids && (pooled || pooled32)) {
+        const int n = row / L;
+        if (pooled_index(ids + (size_t)n * L, L, eos, red_i) == row - n * L) {
+#pragma unroll
+            for (int i = 0; i < PER; ++i) {
+                const int c = threadIdx.x + i * kRowThreads;
+                if (c < C) {
+                    if (pooled) store_from_f32(pooled, (size_t)n * C + c, y_dt, v[i]);
+                    if (pooled32) pooled32[(size_t)n * C + c] = v[i];
+                }
+            }
+        }
+    }
+}
+
+// the C <= 1024 kernel is kept as written before text_final_body existed: routed through the body, hipcc commutes three adds of the
+// row sum and the ISA would no longer be the SD-1.5 encoder's
 __global__ __launch_bounds__(kRowThreads) void text_final_kernel(const void* __restrict__ x, int x_dt, int C, const float* __restrict__ g,
                                                                  const float* __restrict__ b, float eps, void* __restrict__ y, int y_dt,
                                                                  const int64_t* __restrict__ ids, int L, int eos, void* __restrict__ pooled) {
@@ -134,6 +193,17 @@ __global__ __launch_bounds__(kRowThreads) void text_final_kernel(const void* __r
             }
         }
     }
+}
+
+// C <= 256 * PER, with the fp32 pooled row
+template <int PER>
+__global__ __launch_bounds__(kRowThreads) void text_final_ext_kernel(const void* __restrict__ x, int x_dt, int C, const float* __restrict__ g,
+                                                                     const float* __restrict__ b, float eps, void* __restrict__ y, int y_dt,
+                                                                     const int64_t* __restrict__ ids, int L, int eos,
+                                                                     void* __restrict__ pooled, float* __restrict__ pooled32) {
+    __shared__ float red[4];
+    __shared__ int red_i;
+    text_final_body<PER>(x, x_dt, C, g, b, eps, y, y_dt, ids, L, eos, pooled, pooled32, red, &red_i);
 }
 
 __global__ void text_store_kernel(const float* __restrict__ x, void* __restrict__ y, int y_dt, size_t n) {
@@ -268,9 +338,14 @@ size_t text_attn_lds(int kpad) { return (size_t)2 * (16 * kQLd + kpad * kQLd + 6
 int op_text_embed(const int64_t* ids, const float* tok, const float* pos, int V, int N, int L, int C, float* x,
                   const float* gamma, const float* beta, float eps, half_t* y, int* bad, hipStream_t s) {
     CTRL_CHECK(ids && tok && pos && x && gamma && beta && y, "text_embed: null argument");
-    CTRL_CHECK(N >= 1 && L >= 1 && V >= 1 && C >= 1 && C <= kRowThreads * kRowPer, "text_embed: bad shape (C <= 1024)");
+    CTRL_CHECK(N >= 1 && L >= 1 && V >= 1 && C >= 1 && (C <= kRowThreads * kRowPer || (C <= kRowThreads * kRowPerWide && C % 64 == 0)),
+               "text_embed: bad shape (C <= 1024, or a multiple of 64 up to 2048)");
     PROF_WORK(0, (double)N * L * C * (4.0 * 2 + 4.0 + 2.0));
-    LAUNCH("text_embed", text_embed_ln_kernel, dim3(N * L), dim3(kRowThreads), 0, s, ids, tok, pos, V, L, C, x, gamma, beta, eps, y, bad);
+    if (C <= kRowThreads * kRowPer)
+        LAUNCH("text_embed", text_embed_ln_kernel, dim3(N * L), dim3(kRowThreads), 0, s, ids, tok, pos, V, L, C, x, gamma, beta, eps, y, bad);
+    else
+        LAUNCH("text_embed", text_embed_ln_wide_kernel, dim3(N * L), dim3(kRowThreads), 0, s, ids, tok, pos, V, L, C, x, gamma, beta, eps, y,
+               bad);
     return 0;
 }
 
@@ -292,13 +367,26 @@ int op_text_attn(const half_t* qkv, long ld, half_t* out, long ldo, int N, int L
 
 int op_text_final(const void* x, int x_dt, int rows, int C, const float* gamma, const float* beta, float eps, void* y, int y_dt,
                   const int64_t* ids, int L, int eos, void* pooled, hipStream_t s) {
-    CTRL_CHECK(x && gamma && beta && (y || pooled), "text_final: null argument");
-    CTRL_CHECK(rows >= 1 && C >= 1 && C <= kRowThreads * kRowPer, "text_final: bad shape (C <= 1024)");
+    return op_text_final_ext(x, x_dt, rows, C, gamma, beta, eps, y, y_dt, ids, L, eos, pooled, nullptr, s);
+}
+
+int op_text_final_ext(const void* x, int x_dt, int rows, int C, const float* gamma, const float* beta, float eps, void* y, int y_dt,
+                      const int64_t* ids, int L, int eos, void* pooled, float* pooled32, hipStream_t s) {
+    CTRL_CHECK(x && gamma && beta && (y || pooled || pooled32), "text_final: null argument");
+    CTRL_CHECK(rows >= 1 && C >= 1 && (C <= kRowThreads * kRowPer || (C <= kRowThreads * kRowPerWide && C % 64 == 0)),
+               "text_final: bad shape (C <= 1024, or a multiple of 64 up to 2048)");
     CTRL_CHECK(x_dt >= DT_F32 && x_dt <= DT_BF16 && y_dt >= DT_F32 && y_dt <= DT_BF16, "text_final: bad dtype");
-    CTRL_CHECK(!pooled || (ids && L >= 1 && rows % L == 0), "text_final: the pooled row needs the ids and rows = N * L");
+    CTRL_CHECK(!(pooled || pooled32) || (ids && L >= 1 && rows % L == 0), "text_final: the pooled row needs the ids and rows = N * L");
     PROF_WORK(0, (double)rows * C * 8.0);
-    LAUNCH("text_final", text_final_kernel, dim3(rows), dim3(kRowThreads), 0, s, x, x_dt, C, gamma, beta, eps, y, y_dt,
-           pooled ? ids : nullptr, L, eos, pooled);
+    const int64_t* pids = (pooled || pooled32) ? ids : nullptr;
+    if (C <= kRowThreads * kRowPer && !pooled32)
+        LAUNCH("text_final", text_final_kernel, dim3(rows), dim3(kRowThreads), 0, s, x, x_dt, C, gamma, beta, eps, y, y_dt, pids, L, eos, pooled);
+    else if (C <= kRowThreads * kRowPer)
+        LAUNCH("text_final", text_final_ext_kernel<kRowPer>, dim3(rows), dim3(kRowThreads), 0, s, x, x_dt, C, gamma, beta, eps, y, y_dt, pids,
+               L, eos, pooled, pooled32);
+    else
+        LAUNCH("text_final", text_final_ext_kernel<kRowPerWide>, dim3(rows), dim3(kRowThreads), 0, s, x, x_dt, C, gamma, beta, eps, y, y_dt,
+               pids, L, eos, pooled, pooled32);
     return 0;
 }
 

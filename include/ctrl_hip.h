@@ -18,6 +18,9 @@
  *                             sdxl_controlnet_adapter_pipeline.py:1306-1309
  *   ctrl_text_encoder_forward replaces the CLIPTextModel call of ControlNetHelper.encode_controlnet_prompt
  *                             model/ctrl_helper.py:300-457 (SD-1.5's CLIP ViT-L/14 text tower)
+ *   ctrl_text_encoder_forward_ext  replaces the two text-tower calls of the SDXL pipeline's encode_prompt
+ *                             sdxl/pipelines/sdxl_controlnet_adapter_pipeline.py:282-515 (CLIP ViT-L and OpenCLIP ViT-bigG with
+ *                             its text_projection)
  * Op-level entry points (ctrl_op_*) expose the individual kernels for parity tests and micro-benchmarks.
  */
 #ifndef CTRL_HIP_H
@@ -491,6 +494,39 @@ int ctrl_op_text_embed(const int64_t* ids, const float* tok, const float* pos, i
 int ctrl_op_text_attn(const void* qkv, int64_t ld, void* out, int64_t ldo, int N, int L, int heads, float scale, void* stream);
 int ctrl_op_text_final_ln(const void* x, int x_dtype, int rows, int C, const float* gamma, const float* beta, float eps,
                           void* y, int y_dtype, const int64_t* ids, int L, int eos_token_id, void* pooled, void* stream);
+/* The embed and final_ln ops accept C <= 1024, or multiples of 64 up to 2048 (wider instantiations; the C <= 1024 kernels are those
+ * of the SD-1.5 encoder). */
+
+/* ---- Text towers beyond SD-1.5 (transformers CLIPTextModelWithProjection: SDXL's OpenCLIP ViT-bigG text_encoder_2, hidden 1280,
+ * exact gelu, a bias-free text_projection) ----
+ * ctrl_text_encoder_create_ext takes the config above plus this extension; hidden_size may be a multiple of 64 up to 2048.  With
+ * projection_dim > 0 the weights include text_projection.weight [projection_dim][hidden] and text_embeds[n] = pooled_fp32[n] .
+ * W_proj^T is computed in fp32 from the fp32 final-LayerNorm row of prompt n (not from the rounded pooled output), per prompt.
+ * gemm_form 0: every linear on the pinned 64 x 64 x 64 implicit GEMM (what ctrl_text_encoder_create uses; exact gelu then runs as a
+ * separate fp32 pass after the GEMM); 1: the few-row split-K GEMM of csrc/text_gemm.hip (weights streamed once over all XCDs, split
+ * and reduction order functions of (N, K) only).  Both are batch-invariant. */
+typedef struct ctrl_text_encoder_ext {
+    int32_t hidden_act;        /* 0 quick_gelu, 1 gelu (erf) */
+    int32_t projection_dim;    /* 0 = none; else text_projection.weight [projection_dim][hidden] */
+    int32_t gemm_form;         /* 0 the pinned form, 1 the few-row GEMM */
+    int32_t reserved;          /* 0 */
+} ctrl_text_encoder_ext;
+int ctrl_text_encoder_create_ext(const ctrl_text_encoder_config* cfg, const ctrl_text_encoder_ext* ext, const ctrl_tensor_ref* tensors,
+                                 int n_tensors, void* stream, ctrl_text_encoder** out);
+/* ctrl_text_encoder_forward plus text_embeds [N][projection_dim] (out_dtype; needs a projection) and a choice of hidden states:
+ * hidden_index -1 writes all num_hidden_layers + 1 states to hidden_states as ctrl_text_encoder_forward does; k in
+ * [0, num_hidden_layers] writes only state k, as [N][L][hidden].  When last_hidden, pooled and text_embeds are all NULL the forward
+ * stops after layer k; the state it writes is bit-identical to a full forward's.  Works on plans of ctrl_text_encoder_create as well.
+ * Never synchronises; capturable once a forward of the same or a larger batch has run eagerly (the workspace does not grow under
+ * capture). */
+int ctrl_text_encoder_forward_ext(ctrl_text_encoder* h, const int64_t* input_ids, int N, int L, void* last_hidden, void* pooled,
+                                  void* text_embeds, void* hidden_states, int hidden_index, int out_dtype, void* stream);
+/* op level (csrc/text_gemm.hip): y [M][N] (y_dtype) = act(x [M][K] W^T + bias) (+ res), x / W fp16 row-major, bias fp32 [N] (NULL =
+ * none), res fp32 [M][N] (NULL = none); act 0 none, 2 quick_gelu, 3 exact gelu; N % 16 == 0, K % 32 == 0, 16-byte aligned pointers.
+ * ws: device scratch of ctrl_text_gemm_ws_bytes(M, N, K) bytes.  Row m of y depends on row m of x alone, bit for bit. */
+int64_t ctrl_text_gemm_ws_bytes(int M, int N, int K);
+int ctrl_op_text_gemm(const void* x, const void* W, const float* bias, int M, int N, int K, int act, const float* res, void* y,
+                      int y_dtype, void* ws, int64_t ws_bytes, void* stream);
 
 /* ---- Router (model/ctrl_router.py) ---- */
 /* weights_out fp32 device [num_routers + (has_mid?1:0)][E]; wg fp32 device same shape (Linear(1,E).weight[:,0]
