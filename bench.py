@@ -6,7 +6,7 @@ pool the latents to 64x64, ControlNetModel.forward (K of them + router + merge i
 ControlNetAdapter.forward -- on synthetic latents / prompts / condition images already resident in HBM and seeded random
 weights of the real architectures (361 M + 184 M / 587 M parameters).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sdxl|svd16|i2vgen16|multi3] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sdxl|svd16|i2vgen16|multi3] [--dump-outputs DIR] [--full]
 
 `--steps K` timed steps give `ms_per_step` (their mean).  `--dump-outputs DIR` writes what the last timed step returned as float32
 DIR/<name>.npy (a seeded sample of each tensor when they would exceed 56 MB together) so that two builds run with the same arguments
@@ -15,7 +15,13 @@ DIR/<name>.npy (a seeded sample of each tensor when they would exceed 56 MB toge
 `--gpus N` with N > 1 launches the N ranks itself (re-executes under `python -m torch.distributed.run`, one rank per
 GPU over RCCL, 127.0.0.1 rendezvous); started under a launcher already (RANK / WORLD_SIZE in the environment) it joins it.
 
-Rank 0 prints the headline as the LAST stdout line, ONE JSON object of about 3 KB (the driver keeps an 8 KB tail of stdout).  Besides the driver contract it carries:
+A plain run does what the headline needs and nothing else: it builds the models, warms up, times the K steps, dumps the
+outputs if asked, and prints the result line.  `--full` adds, after the timed region, every other leg: the median over
+single steps, the fused entry point, the per-kernel / roofline leg, the CPU baseline with its parity check, and the other
+BASELINE workloads (`--no-cpu-baseline` / `--no-other-workloads` drop those two from a full run).  A plain run leaves their
+fields of the line null and writes no per-kernel file.
+
+Rank 0 prints the headline as the LAST stdout line, ONE JSON object (about 3 KB with --full; the driver keeps an 8 KB tail of stdout).  Besides the driver contract a --full run carries:
   roofline      ONE kernel (symbol with template arguments + shape): algorithmic FLOPs per launch / HIP-event time per
                 launch on the launch stream, vs the dense fp16 MFMA peak; `traffic` = PMC HBM bytes per launch of that
                 kernel from the committed rocprofv3 passes (profiles/, tools/profile_round.sh)
@@ -252,11 +258,15 @@ def main():
     ap.add_argument("--batch", type=int, default=8, help="sdxl: images per GPU entering the hot path (BASELINE: 8)")
     ap.add_argument("--workload", default="sdxl", choices=sorted(WORKLOADS))
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of a captured hipGraph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the median, fused-step, per-kernel / roofline, CPU-baseline / parity and "
+                         "other-workload legs (off: the run does only what the headline needs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline / parity leg")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="skip the svd16 / i2vgen16 / multi3 / sdxl b=16 legs the default invocation times after the headline")
-    ap.add_argument("--per-kernel-out", default=os.path.join(ROOT, "bench_per_kernel.json"),
-                    help="where rank 0 writes the per-kernel / per-class tables (they are too long for the headline line)")
+                    help="--full: skip the svd16 / i2vgen16 / multi3 / sdxl b=16 legs it times after the headline")
+    ap.add_argument("--per-kernel-out", default=None,
+                    help="--full: where rank 0 writes the per-kernel / per-class tables (they are too long for the headline line; "
+                         "default bench_per_kernel.json next to this script)")
     ap.add_argument("--clip-split", action="store_true",
                     help="video workloads: ONE clip for the whole job, its 16 frames sharded over the --gpus ranks (frame-mixing "
                          "ops exchange over RCCL: all_to_all around the temporal transformers, Conv3d halo, GroupNorm "
@@ -276,6 +286,10 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         raise SystemExit("--steps must be at least 1")
+    if not args.full and (args.per_kernel_out is not None or args.profile_scope != "step"):
+        raise SystemExit("--per-kernel-out / --profile-scope configure the per-kernel leg: it runs with --full only")
+    if args.per_kernel_out is None:
+        args.per_kernel_out = os.path.join(ROOT, "bench_per_kernel.json")
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args))
@@ -393,9 +407,10 @@ def main():
     if comm is not None:
         value = args.steps / elapsed                                 # ONE clip for the whole job: strong scaling
     # the median over single steps ("median of >= 20"), taken AFTER the timed region with an event pair per step on
-    # the launch stream; reported beside the contract's mean-of-K `ms_per_step`, never instead of it
+    # the launch stream; reported beside the contract's mean-of-K `ms_per_step`, never instead of it.  This and every leg below run
+    # with --full only: a plain run goes straight to the result line
     median_ms = None
-    if rank == 0 and comm is None:
+    if args.full and rank == 0 and comm is None:
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(max(args.steps, 20))]
         for e0, e1 in evs:
             e0.record()
@@ -408,7 +423,7 @@ def main():
     # what the LAST graph replay wrote (the timed artifact itself: replay number warmup + steps + len(evs)), copied out before
     # anything else runs on these plans -- compared with the oracle in the cpu_baseline leg below
     replay_out, replays = None, 0
-    if rank == 0 and mode == "hipgraph" and comm is None and not args.fused:
+    if args.full and rank == 0 and mode == "hipgraph" and comm is None and not args.fused:
         replays = args.warmup + args.steps + max(args.steps, 20)
         (gd, gm), (ga, gam) = static_out
         torch.cuda.synchronize()
@@ -417,7 +432,7 @@ def main():
     # ---- the same step through the fused entry point (ControlNet on its own stream, adapter blocks start when their input
     #      exists): same arithmetic, bit-identical results; reported beside the headline, never as `value` ----
     fused = None
-    if w["n_cn"] == 1 and not args.fused and not args.no_graph and comm is None:
+    if args.full and w["n_cn"] == 1 and not args.fused and not args.no_graph and comm is None:
         try:
             for _ in range(2):
                 step_fused()
@@ -437,7 +452,7 @@ def main():
     # ---- roofline leg: eager steps with HIP events around every launch, on the launch stream (lanes off) ----
     kernels, per_kernel, roof = {}, [], None
     below_quarter_ms, below_quarter_launches = 0.0, 0.0
-    if rank == 0:
+    if args.full and rank == 0:
         from ctrl_adapter_amd import ops
         reps = 3
         if args.profile_scope == "step":
@@ -504,7 +519,7 @@ def main():
     # ---- cpu_baseline leg: the fp32 oracle on the host cores, ONE pass over the whole step of this workload (rank 0, N=1
     #      only) on the very inputs the HIP step was timed on; its outputs are the parity check of the benched configuration ----
     cpu, parity = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and comm is None:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and comm is None:
         import cases  # noqa: F401
         from oracle.init import seeded_init
         from oracle.controlnet import ControlNetOracle
@@ -579,9 +594,9 @@ def main():
                           what="HIP step (eager; these plans, these %d distinct inputs) vs fp32 oracle -> oracle chain" % n)
 
     # ---- the other north-star workloads (BASELINE configs 3, 4, 5 and the CFG-doubled SDXL batch), after the headline's timed
-    #      region, the default single-GPU invocation only (the N > 1 scaling runs stay short): `other_workloads` of the headline ----
+    #      region, the --full single-GPU invocation only (the N > 1 scaling runs stay short): `other_workloads` of the headline ----
     others = None
-    if args.workload == "sdxl" and args.batch == 8 and world == 1 and comm is None and not args.no_graph and not args.fused and not args.no_other_workloads:
+    if args.full and args.workload == "sdxl" and args.batch == 8 and world == 1 and comm is None and not args.no_graph and not args.fused and not args.no_other_workloads:
         others = {}
         for name, wn, b in (("svd16", "svd16", 0), ("i2vgen16", "i2vgen16", 0), ("multi3", "multi3", 0), ("sdxl_b16", "sdxl", 16),
                                ("sdxl_b2_cfg_pair", "sdxl", 2)):      # (the last one: BASELINE config 1's shape, one image + its CFG twin)
@@ -617,18 +632,18 @@ def main():
                 print("bench: per-kernel table not written (%s)" % e, file=sys.stderr)
         top = [{"kernel": r["kernel"][:96], "ms_per_step": r["ms_per_step"], "frac": r["frac"]} for r in per_kernel[1:4]]
         launches = int(round(sum(v["launches_per_step"] for v in kernels.values()))) if kernels else None
-        hbm_gb, hbm_src = pmc_total_for(args.workload) if args.batch == 8 and comm is None else (None, None)
+        hbm_gb, hbm_src = pmc_total_for(args.workload) if args.full and args.batch == 8 and comm is None else (None, None)
         line = {
             "metric": w["metric"], "value": round(value, 3), "unit": "denoise-steps/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "ms_per_step_median": median_ms, "higher_is_better": True,
-            "scaling": "strong" if comm is not None else "weak",
+            "scaling": "strong" if comm is not None else "weak", "full": args.full,
             "vs_baseline": None,
             "dtype": "f16",    # MFMA operands fp16; fp32 accumulate / statistics / softmax / residual streams
             "data": "synthetic latents, prompts, condition images; seeded random weights",
             "config": {"workload": args.workload + ": " + ((w["what"] % (n, n)) if "%d" in w["what"] else w["what"])[:150],
                        "baseline_config": w["config"], "batch_per_gpu": n,
                        "parallelism": ("one clip, frames sharded over %d ranks: all_to_all / halo / all-reduce over RCCL, %.0f MB sent "
-                                       "per rank and step" % (world, comm.bytes_sent / max(1, args.steps + args.warmup + 2 + 3) / 1e6))
+                                       "per rank and step" % (world, comm.bytes_sent / max(1, args.steps + args.warmup + 2 + (3 if args.full else 0)) / 1e6))
                        if comm is not None else "dp%d, no collective" % world,
                        "launch": mode, "call_form": "controlnet(...) ; adapter(...)" if not args.fused else "controlled_step(...)"},
             "algorithmic_tflop_per_step": round(flops_step / 1e12, 2),

@@ -1,7 +1,7 @@
 mkdir -p gpurun_out/r5c; O=gpurun_out/r5c
 (python -m pytest tests/test_gpu_ops.py -m gpu -q --tb=short -s 2>&1 | grep -E "PARITY qkv one|PARITY groupnorm fused|PARITY conv3x3_small|passed|failed|FAILED|Error|assert|rror:" | tail -60) > $O/ops.log
 (python -m pytest tests/test_gpu_e2e.py -m gpu -q --tb=short -s -k "grouped or golden or controlled_step or text_kv or full_size_sdxl or sdxl_batch8 or video_chain_at_benched or multi_condition_and_i2vgen" 2>&1 | grep -E "PARITY|passed|failed|FAILED|Error|assert|rror:" | tail -70) > $O/e2e.log
-B="python bench.py --no-other-workloads --no-cpu-baseline --steps 20 --warmup 5"
+B="python bench.py --full --no-other-workloads --no-cpu-baseline --steps 20 --warmup 5"
 $B --per-kernel-out $O/pk_default.json > $O/b_default.json 2>> $O/bench.err
 CTRL_GROUP=0 $B --per-kernel-out $O/pk_nogroup.json > $O/b_nogroup.json 2>> $O/bench.err
 CTRL_SMALL_TILES=0 $B --per-kernel-out $O/pk_tmp.json > $O/b_nosmalltiles.json 2>> $O/bench.err

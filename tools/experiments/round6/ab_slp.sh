@@ -5,8 +5,8 @@ O=gpurun_out/slp; mkdir -p $O
 run() {   # $1 = tag
   timeout 200 tools/bin/attn_bench $O/attn_$1.txt 0,2,3,12 > /dev/null 2>&1
   timeout 120 tools/bin/ffn_bench $O/ffn_$1.txt > /dev/null 2>&1
-  for i in 1 2; do timeout 300 python bench.py --no-cpu-baseline --no-other-workloads 2>/dev/null | tail -1 > $O/bench_$1_$i.json; done
-  timeout 300 python bench.py --workload svd16 --no-cpu-baseline --no-other-workloads 2>/dev/null | tail -1 > $O/bench_svd_$1.json
+  for i in 1 2; do timeout 300 python bench.py --full --no-cpu-baseline --no-other-workloads 2>/dev/null | tail -1 > $O/bench_$1_$i.json; done
+  timeout 300 python bench.py --full --workload svd16 --no-cpu-baseline --no-other-workloads 2>/dev/null | tail -1 > $O/bench_svd_$1.json
 }
 run noslp
 CTRL_BUILD_SLP=1 CTRL_BUILD_AUDIT=0 python ctrl-adapter_amd/build.py | tail -1

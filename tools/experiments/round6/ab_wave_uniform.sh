@@ -4,7 +4,7 @@
 O=gpurun_out/wave; mkdir -p $O
 run() {
   timeout 200 tools/bin/attn_bench $O/attn_$1.txt 0,2 > /dev/null 2>&1
-  for i in 1 2; do timeout 300 python bench.py --no-cpu-baseline --no-other-workloads 2>/dev/null | tail -1 > $O/bench_$1_$i.json; done
+  for i in 1 2; do timeout 300 python bench.py --full --no-cpu-baseline --no-other-workloads 2>/dev/null | tail -1 > $O/bench_$1_$i.json; done
 }
 run new
 sed -i 's/wave = __builtin_amdgcn_readfirstlane(tid >> 6);/wave = tid >> 6;/' ctrl-adapter_amd/csrc/attention_d64.hip ctrl-adapter_amd/csrc/attention.hip
