@@ -84,6 +84,15 @@ class TextEncoderExt(C.Structure):
     _fields_ = [("hidden_act", C.c_int32), ("projection_dim", C.c_int32), ("gemm_form", C.c_int32), ("reserved", C.c_int32)]
 
 
+class VisionEncoderConfig(C.Structure):
+    _fields_ = [("image_size", C.c_int32), ("patch_size", C.c_int32), ("hidden_size", C.c_int32), ("intermediate_size", C.c_int32),
+                ("num_hidden_layers", C.c_int32), ("num_attention_heads", C.c_int32), ("projection_dim", C.c_int32),
+                ("hidden_act", C.c_int32), ("layer_norm_eps", C.c_float), ("gemm_form", C.c_int32)]
+
+
+U8_NHWC = 3     # pixel dtype of ctrl_vision_encoder_forward / the vision ops: uint8 [N][H][W][3]
+
+
 CB_GATHER = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p)
 CB_REDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)
 CB_HALO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p)
@@ -116,6 +125,8 @@ EXPORTS = [
     "ctrl_text_encoder_create", "ctrl_text_encoder_destroy", "ctrl_text_encoder_forward", "ctrl_text_encoder_id_status",
     "ctrl_op_text_embed", "ctrl_op_text_attn", "ctrl_op_text_final_ln",
     "ctrl_text_encoder_create_ext", "ctrl_text_encoder_forward_ext", "ctrl_text_gemm_ws_bytes", "ctrl_op_text_gemm",
+    "ctrl_vision_encoder_param_count", "ctrl_vision_encoder_param_spec", "ctrl_vision_encoder_create", "ctrl_vision_encoder_destroy",
+    "ctrl_vision_encoder_forward", "ctrl_op_vision_patchify", "ctrl_op_vision_embed", "ctrl_op_vision_cls_ln", "ctrl_op_clip_resize_aa",
 ]
 
 _lib = None
@@ -134,7 +145,7 @@ def lib():
         for name in EXPORTS:
             fn = getattr(_lib, name)
             if name not in ("ctrl_last_error", "ctrl_policy_get", "ctrl_policy_name", "ctrl_controlnet_destroy", "ctrl_adapter_destroy", "ctrl_rccl_comm_destroy", "ctrl_rccl_comm_bytes_sent",
-                            "ctrl_text_encoder_destroy"):
+                            "ctrl_text_encoder_destroy", "ctrl_vision_encoder_destroy"):
                 fn.restype = C.c_int
         _lib.ctrl_policy_get.restype = C.c_char_p
         _lib.ctrl_policy_get.argtypes = [C.c_char_p]
@@ -156,6 +167,18 @@ def lib():
         _lib.ctrl_text_gemm_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
         _lib.ctrl_op_text_gemm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                            C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+        _lib.ctrl_vision_encoder_destroy.restype = None
+        _lib.ctrl_vision_encoder_destroy.argtypes = [C.c_void_p]
+        _lib.ctrl_vision_encoder_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        _lib.ctrl_op_vision_patchify.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                 C.c_void_p]
+        _lib.ctrl_op_vision_embed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ctrl_op_vision_cls_ln.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
+                                               C.c_int, C.c_void_p, C.c_void_p]
+        _lib.ctrl_op_clip_resize_aa.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                C.c_void_p, C.c_int, C.c_void_p]
         _lib.ctrl_rccl_comm_destroy.restype = None
         _lib.ctrl_rccl_comm_destroy.argtypes = [C.c_void_p]
         _lib.ctrl_rccl_comm_bytes_sent.restype = C.c_int64

@@ -129,6 +129,20 @@ int op_text_gemm_finish(const float* ws, int splits, int M, int N, const float* 
 // text_embeds[n] = pooled32[n] . Wp^T in fp32 (Wp fp32 [P][C], no bias), out [N][P] in out_dt
 int op_text_proj(const float* pooled32, const float* Wp, int N, int C, int P, void* out, int out_dt, hipStream_t s);
 
+// CLIP vision tower (vision.hip): pixels (fp32 / fp16 / bf16 NCHW, or uint8 NHWC / 255) -> im2col rows [N*P][Kpad] fp16, normalised
+// (x - mean_c) / std_c in fp32 when mean_std (host, mean[3] | std[3]) is given; [class ; patch rows] + position -> pre_layrnorm (fp32 x)
+// -> layer_norm1 (fp16 y); V of the row-major Q | K | V rows -> V^T [N][C][Lkpad] (pad columns zero); post_layernorm of every image's
+// row 0 (pooled in y_dt and / or fp32); SVD's _resize_with_antialiasing + (x + 1) / 2 + optional normalise -> [N][3][OH][OW] in out_dt;
+// the patch weight [C][K] fp32 -> fp16 [C][Kpad]
+int op_vision_patchify(const void* px, int dt, int N, int S, int p, const float* mean_std, half_t* out, int Kpad, hipStream_t s);
+int op_vision_embed(const float* patch, const float* cls, const float* pos, int N, int L, int C, const float* g0, const float* b0,
+                    const float* g1, const float* b1, float eps, float* x, half_t* y, hipStream_t s);
+int op_vision_vt(const half_t* v, long ld, half_t* vt, int N, int L, int C, int Lkpad, hipStream_t s);
+int op_vision_cls_ln(const float* x, int N, int L, int C, const float* g, const float* b, float eps, void* pooled, int y_dt, float* pooled32,
+                     hipStream_t s);
+int op_clip_resize_aa(const void* src, int dt, int N, int H, int W, int OH, int OW, const float* mean_std, void* out, int out_dt, hipStream_t s);
+int op_vision_pack_patch(const float* w, int C, int K, int Kpad, half_t* out, hipStream_t s);
+
 // temporal attention over the frame axis: tokens X [(b*F+f)*HW + p][...]; seq = F (<= 32)
 typedef ctrl_tattn_desc TAttnArgs;
 int op_temporal_attn(const TAttnArgs& a, hipStream_t s);

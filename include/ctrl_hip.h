@@ -21,6 +21,8 @@
  *   ctrl_text_encoder_forward_ext  replaces the two text-tower calls of the SDXL pipeline's encode_prompt
  *                             sdxl/pipelines/sdxl_controlnet_adapter_pipeline.py:282-515 (CLIP ViT-L and OpenCLIP ViT-bigG with
  *                             its text_projection)
+ *   ctrl_vision_encoder_forward replaces the image_encoder call of the SVD / I2VGen-XL pipelines' _encode_image
+ *                             svd/pipelines/svd_controlnet_adapter_pipeline.py:166-212, i2vgen_xl/...:366-396 (CLIP ViT-H/14)
  * Op-level entry points (ctrl_op_*) expose the individual kernels for parity tests and micro-benchmarks.
  */
 #ifndef CTRL_HIP_H
@@ -527,6 +529,56 @@ int ctrl_text_encoder_forward_ext(ctrl_text_encoder* h, const int64_t* input_ids
 int64_t ctrl_text_gemm_ws_bytes(int M, int N, int K);
 int ctrl_op_text_gemm(const void* x, const void* W, const float* bias, int M, int N, int K, int act, const float* res, void* y,
                       int y_dtype, void* ws, int64_t ws_bytes, void* stream);
+
+/* ---- CLIP vision tower (transformers CLIPVisionModelWithProjection: the image_encoder of SVD and I2VGen-XL, CLIP ViT-H/14;
+ * svd/pipelines/svd_controlnet_adapter_pipeline.py:166-212, i2vgen_xl/pipelines/i2vgen_xl_controlnet_adapter_pipeline.py:366-396) ----
+ * emb = [class_embedding ; patch_conv(pixels)] + position_embedding; x = pre_layrnorm(emb); pre-LN layers as in the text tower but
+ * non-causal (flash attention, head_dim 40 / 64 / 80 / 160); last_hidden_state = x (no final LayerNorm); pooled = post_layernorm(x[:, 0]);
+ * image_embeds = pooled_fp32 . visual_projection^T (fp32, no bias).  Residual stream fp32, GEMM operands fp16.  hidden_size a multiple
+ * of 64 up to 2048, image_size % patch_size == 0, (image_size / patch_size)^2 + 1 <= 577 tokens. */
+enum { CTRL_U8_NHWC = 3 };           /* pixel dtype: uint8 [N][H][W][3] (PIL's layout), read as x / 255 */
+typedef struct ctrl_vision_encoder_config {
+    int32_t image_size;                /* 224 */
+    int32_t patch_size;                /* 14 */
+    int32_t hidden_size;               /* 1280 */
+    int32_t intermediate_size;         /* 5120 */
+    int32_t num_hidden_layers;         /* 32 */
+    int32_t num_attention_heads;       /* 16 */
+    int32_t projection_dim;            /* 1024 */
+    int32_t hidden_act;                /* 0 quick_gelu, 1 gelu (erf) */
+    float layer_norm_eps;              /* 1e-5 */
+    int32_t gemm_form;                 /* 0 the pinned implicit GEMM, 1 the few-row split-K GEMM (csrc/text_gemm.hip) */
+} ctrl_vision_encoder_config;
+typedef struct ctrl_vision_encoder ctrl_vision_encoder;   /* opaque */
+/* parameter inventory under transformers' keys (vision_model.embeddings.class_embedding, ..., visual_projection.weight) */
+int ctrl_vision_encoder_param_count(const ctrl_vision_encoder_config* cfg);
+int ctrl_vision_encoder_param_spec(const ctrl_vision_encoder_config* cfg, int i, char* name, int name_len, int64_t shape[6], int* ndim);
+int ctrl_vision_encoder_create(const ctrl_vision_encoder_config* cfg, const ctrl_tensor_ref* tensors, int n_tensors, void* stream,
+                               ctrl_vision_encoder** out);
+void ctrl_vision_encoder_destroy(ctrl_vision_encoder* h);
+/* pixels [N][3][S][S] (pixel_dtype CTRL_F32 / F16 / BF16) or [N][S][S][3] (CTRL_U8_NHWC), S = image_size, device memory.
+ * mean_std (host, mean[3] then std[3]; NULL = the pixels are already normalised): (x - mean_c) / std_c in fp32 before the one rounding
+ * to fp16.  Outputs in out_dtype (NULL = not written): last_hidden [N][L][hidden], pooled [N][hidden], image_embeds [N][projection_dim],
+ * hidden_states as in ctrl_text_encoder_forward_ext (hidden_index -1: all num_hidden_layers + 1 states [layers + 1][N][L][hidden], k:
+ * state k alone [N][L][hidden]; with no other output the layers after k are not run).  Every image is computed by the same instruction
+ * sequence whatever N (both gemm forms).  Never synchronises; capturable once a forward of the same or a larger batch ran eagerly. */
+int ctrl_vision_encoder_forward(ctrl_vision_encoder* h, const void* pixels, int pixel_dtype, int N, const float* mean_std,
+                                void* last_hidden, void* pooled, void* image_embeds, void* hidden_states, int hidden_index,
+                                int out_dtype, void* stream);
+/* op level (csrc/vision.hip).  patchify: pixels as above -> im2col rows out fp16 [N * (S/p)^2][Kpad] (column c*p*p + ky*p + kx, zero from
+ * 3*p*p on; Kpad a multiple of 64), optionally normalised.  embed: x fp32 [N*L][C] = pre_layrnorm([cls ; patch [N*(L-1)][C]] + pos [L][C]),
+ * y fp16 = LayerNorm(x; g1, b1).  cls_ln: post-LayerNorm of row 0 of every image of x fp32 [N][L][C] into pooled (out_dtype) and
+ * pooled32 (fp32), either may be NULL.  resize_aa: SVD's _resize_with_antialiasing on x * 2 - 1 (Gaussian blur with reflect padding,
+ * bicubic align_corners), then (x + 1) / 2 and the optional normalisation -> out [N][3][OH][OW] in out_dtype; src fp32 / fp16 / bf16
+ * NCHW in [0, 1] or uint8 NHWC. */
+int ctrl_op_vision_patchify(const void* pixels, int pixel_dtype, int N, int image_size, int patch_size, const float* mean_std, void* out,
+                            int Kpad, void* stream);
+int ctrl_op_vision_embed(const float* patch_out, const float* class_embedding, const float* pos, int N, int L, int C, const float* pre_g,
+                         const float* pre_b, const float* ln1_g, const float* ln1_b, float eps, float* x, void* y, void* stream);
+int ctrl_op_vision_cls_ln(const float* x, int N, int L, int C, const float* gamma, const float* beta, float eps, void* pooled,
+                          int out_dtype, float* pooled32, void* stream);
+int ctrl_op_clip_resize_aa(const void* src, int src_dtype, int N, int H, int W, int OH, int OW, const float* mean_std, void* out,
+                           int out_dtype, void* stream);
 
 /* ---- Router (model/ctrl_router.py) ---- */
 /* weights_out fp32 device [num_routers + (has_mid?1:0)][E]; wg fp32 device same shape (Linear(1,E).weight[:,0]
