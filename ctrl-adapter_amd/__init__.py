@@ -9,3 +9,4 @@ from .image_prep import prepare_images  # noqa: F401
 from .text_encoder import CLIPTextModel, CLIPTextOutput, encode_controlnet_prompt  # noqa: F401
 from .text_encoder import CLIPTextModelWithProjection, CLIPTextModelOutput, encode_sdxl_prompt  # noqa: F401
 from .vision_encoder import CLIPVisionModelWithProjection, CLIPVisionModelOutput, encode_i2vgen_image, encode_svd_image  # noqa: F401
+from .vae_encoder import AutoencoderKLEncoder, encode_svd_image_latents, prepare_i2vgen_image_latents  # noqa: F401

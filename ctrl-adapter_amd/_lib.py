@@ -22,7 +22,7 @@ class IGemmDesc(C.Structure):
     _fields_ = [("A", C.c_void_p), ("lda", C.c_int64), ("mode", C.c_int32), ("Cin", C.c_int32), ("taps", C.c_int32),
                 ("Hin", C.c_int32), ("Win", C.c_int32), ("Hout", C.c_int32), ("Wout", C.c_int32),
                 ("stride", C.c_int32), ("up", C.c_int32), ("F", C.c_int32), ("HW", C.c_int32), ("t_pad", C.c_int32),
-                ("W", C.c_void_p), ("M", C.c_int32), ("Nout", C.c_int32), ("Ktot", C.c_int32), ("pad1_", C.c_int32),
+                ("W", C.c_void_p), ("M", C.c_int32), ("Nout", C.c_int32), ("Ktot", C.c_int32), ("tap_origin", C.c_int32),
                 ("bias", C.c_void_p), ("rowvec", C.c_void_p), ("rowvec_ld", C.c_int32), ("rows_per_img", C.c_int32),
                 ("res", C.c_void_p), ("ldres", C.c_int64), ("scale", C.c_float), ("geglu", C.c_int32),
                 ("nseg", C.c_int32), ("act", C.c_int32), ("res_f32", C.c_int32), ("a_split", C.c_int32),
@@ -90,6 +90,14 @@ class VisionEncoderConfig(C.Structure):
                 ("hidden_act", C.c_int32), ("layer_norm_eps", C.c_float), ("gemm_form", C.c_int32)]
 
 
+class VaeEncoderConfig(C.Structure):
+    _fields_ = [("num_levels", C.c_int32), ("block_out_channels", C.c_int32 * 4), ("layers_per_block", C.c_int32),
+                ("latent_channels", C.c_int32), ("norm_num_groups", C.c_int32), ("norm_eps", C.c_float)]
+
+
+VAE_MODE, VAE_SAMPLE, VAE_MOMENTS = 0, 1, 2      # output kinds of ctrl_vae_encoder_forward / ctrl_op_vae_posterior
+
+
 U8_NHWC = 3     # pixel dtype of ctrl_vision_encoder_forward / the vision ops: uint8 [N][H][W][3]
 
 
@@ -127,6 +135,8 @@ EXPORTS = [
     "ctrl_text_encoder_create_ext", "ctrl_text_encoder_forward_ext", "ctrl_text_gemm_ws_bytes", "ctrl_op_text_gemm",
     "ctrl_vision_encoder_param_count", "ctrl_vision_encoder_param_spec", "ctrl_vision_encoder_create", "ctrl_vision_encoder_destroy",
     "ctrl_vision_encoder_forward", "ctrl_op_vision_patchify", "ctrl_op_vision_embed", "ctrl_op_vision_cls_ln", "ctrl_op_clip_resize_aa",
+    "ctrl_vae_encoder_param_count", "ctrl_vae_encoder_param_spec", "ctrl_vae_encoder_create", "ctrl_vae_encoder_destroy",
+    "ctrl_vae_encoder_forward", "ctrl_op_vae_row_softmax", "ctrl_op_vae_posterior",
 ]
 
 _lib = None
@@ -145,7 +155,7 @@ def lib():
         for name in EXPORTS:
             fn = getattr(_lib, name)
             if name not in ("ctrl_last_error", "ctrl_policy_get", "ctrl_policy_name", "ctrl_controlnet_destroy", "ctrl_adapter_destroy", "ctrl_rccl_comm_destroy", "ctrl_rccl_comm_bytes_sent",
-                            "ctrl_text_encoder_destroy", "ctrl_vision_encoder_destroy"):
+                            "ctrl_text_encoder_destroy", "ctrl_vision_encoder_destroy", "ctrl_vae_encoder_destroy"):
                 fn.restype = C.c_int
         _lib.ctrl_policy_get.restype = C.c_char_p
         _lib.ctrl_policy_get.argtypes = [C.c_char_p]
@@ -179,6 +189,13 @@ def lib():
                                                C.c_int, C.c_void_p, C.c_void_p]
         _lib.ctrl_op_clip_resize_aa.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                 C.c_void_p, C.c_int, C.c_void_p]
+        _lib.ctrl_vae_encoder_destroy.restype = None
+        _lib.ctrl_vae_encoder_destroy.argtypes = [C.c_void_p]
+        _lib.ctrl_vae_encoder_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                  C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        _lib.ctrl_op_vae_row_softmax.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        _lib.ctrl_op_vae_posterior.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                               C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         _lib.ctrl_rccl_comm_destroy.restype = None
         _lib.ctrl_rccl_comm_destroy.argtypes = [C.c_void_p]
         _lib.ctrl_rccl_comm_bytes_sent.restype = C.c_int64

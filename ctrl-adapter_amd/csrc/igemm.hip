@@ -4,7 +4,7 @@
 //   * Linear / 1x1 conv            (IG_ROWS)      -- reference: every nn.Linear / Conv2d(k=1) under
 //                                                     controlnet/controlnet.py:366-424 and
 //                                                     model/adapter_spatial_temporal.py:56-69
-//   * 3x3 conv, stride 1|2, pad 1, optional nearest x2 up-sampling folded into the gather
+//   * 3x3 conv, stride 1|2, pad 1 (or Downsample2D's right / bottom pad: tap_origin), optional nearest x2 up-sampling folded into the gather
 //                                   (IG_CONV2D)    -- model/resnet_block_2d.py:164-221 (conv1/conv2,
 //                                                     Upsample2D), diffusers Downsample2D
 //   * Conv3d (3,1,1) over frames    (IG_TEMPORAL)  -- TemporalResnetBlock, adapter_spatial_temporal.py:96-104
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (MinWaves<BM, BN, WAVES_M *
     int a_y[APASS], a_x[APASS];          // CONV2D: oy*stride-pad, ox*stride-pad; TEMPORAL: a_y = frame index
     bool a_ok[APASS];
     int a_c8[APASS];                     // source chunk (halfs) after the swizzle
-    const int pad = (a.taps == 9) ? 1 : 0;
+    const int pad = (a.taps == 9 && !a.tap_origin) ? 1 : 0;     // tap_origin 1: taps start at stride*o (Downsample2D)
     size_t b_off[BPASS];
     bool b_ok[BPASS];
     int b_c8[BPASS];
@@ -440,7 +440,7 @@ __global__ __launch_bounds__(512, 2) void igemm8_kernel(IGemmGroup kargs, int pe
     const int lrow = lane >> 3, lpos = lane & 7;
     // the chunk swizzle of LDS row j is (j >> 1) & 7 = ((wave & 1) * 4 + lrow / 2) & 7 for every pass: one swizzled source chunk per lane
     const int c8b = ((lpos ^ ((((wave & 1) << 2) + (lrow >> 1)) & 7)) * 8) * 2;        // bytes
-    const int pad = (a.taps == 9) ? 1 : 0;
+    const int pad = (a.taps == 9 && !a.tap_origin) ? 1 : 0;     // tap_origin 1: taps start at stride*o (Downsample2D)
     const int VH = a.Hin * a.up, VW = a.Win * a.up;
     const int ushift = (a.up == 2) ? 1 : 0;
     const int lda2 = (int)a.lda * 2;
@@ -1296,7 +1296,7 @@ static bool igemm_same_form(const IGemmArgs& x, const IGemmArgs& y) {
 #define SAME(f) (x.f == y.f)
 #define SAMEP(f) (pk((const void*)x.f) == pk((const void*)y.f))
     bool ok = SAME(lda) && SAME(mode) && SAME(Cin) && SAME(taps) && SAME(Hin) && SAME(Win) && SAME(Hout) && SAME(Wout) && SAME(stride) &&
-              SAME(up) && SAME(F) && SAME(HW) && SAME(t_pad) && SAME(M) && SAME(Nout) && SAME(Ktot) && SAME(rowvec_ld) && SAME(rows_per_img) &&
+              SAME(up) && SAME(tap_origin) && SAME(F) && SAME(HW) && SAME(t_pad) && SAME(M) && SAME(Nout) && SAME(Ktot) && SAME(rowvec_ld) && SAME(rows_per_img) &&
               SAME(ldres) && SAME(scale) && SAME(geglu) && SAME(nseg) && SAME(act) && SAME(res_f32) && SAME(a_split) &&
               SAME(splitk_ws_bytes) && SAME(ld16) && SAME(ld_blend) && SAME(blend_f32) && SAME(out16_lo_off) && SAME(scale2) &&
               SAME(scale2_from) && SAME(scale2_to) && SAME(res_up) &&
@@ -1370,11 +1370,13 @@ static int igemm_validate(const IGemmArgs& a) {
     if (a.mode == IG_CONV2D) {
         CTRL_CHECK(a.taps == 9 || a.taps == 1, "igemm conv2d: taps must be 1 or 9");
         CTRL_CHECK((a.up == 1 || a.up == 2) && (a.stride == 1 || a.stride == 2), "igemm conv2d: up/stride must be 1|2");
+        CTRL_CHECK(a.tap_origin == 0 || (a.tap_origin == 1 && a.taps == 9), "igemm conv2d: tap_origin must be 0, or 1 for a 3x3 conv");
     } else if (a.mode == IG_TEMPORAL) {
         CTRL_CHECK(a.taps == 3 && a.F > 0 && a.HW > 0, "igemm temporal: taps must be 3");
     } else {
         CTRL_CHECK(a.taps == 1, "igemm rows: taps must be 1");
     }
+    CTRL_CHECK(a.tap_origin == 0 || a.mode == IG_CONV2D, "igemm: tap_origin applies to conv2d problems only");
     return 0;
 }
 

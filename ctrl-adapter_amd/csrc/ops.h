@@ -143,6 +143,16 @@ int op_vision_cls_ln(const float* x, int N, int L, int C, const float* g, const 
 int op_clip_resize_aa(const void* src, int dt, int N, int H, int W, int OH, int OW, const float* mean_std, void* out, int out_dt, hipStream_t s);
 int op_vision_pack_patch(const float* w, int C, int K, int Kpad, half_t* out, hipStream_t s);
 
+// KL-VAE encoder (vae.hip): the mid-block attention's softmax -- P fp16 [rows][ldp] = softmax over the first L columns of the fp32
+// scores S [rows][lds], in fp32 (diffusers' upcast_softmax), columns L .. Lpad zeroed; the posterior head -- conv_out rows (NHWC fp32
+// [N*h*w][ldx], x_nchw 0) or MOMENTS planes ([N][ldx][h][w], x_nchw 1) -> quant_conv (wq [2lat][2lat] + bq, fp32; NULL = none) ->
+// DiagonalGaussianDistribution -> mode / sample / moments NCHW in out_dt (include/ctrl_hip.h: CTRL_VAE_*)
+// conv_in of one image: NCHW pixels [3][H][W] (dt) -> fp32 NHWC [H*W][Cout]; w fp32 [9][3][Cout] (op_pack_conv_w_direct), b [Cout]
+int op_vae_conv_in(const void* px, int dt, const float* w, const float* b, float* out, int H, int W, int Cout, hipStream_t s);
+int op_vae_row_softmax(const float* S, long lds, half_t* P, long ldp, int rows, int L, int Lpad, hipStream_t s);
+int op_vae_posterior(const float* x, long ldx, int x_nchw, const float* wq, const float* bq, int N, int lat, int h, int w, const void* eps,
+                     int eps_dt, float scale, int kind, void* out, int out_dt, hipStream_t s);
+
 // temporal attention over the frame axis: tokens X [(b*F+f)*HW + p][...]; seq = F (<= 32)
 typedef ctrl_tattn_desc TAttnArgs;
 int op_temporal_attn(const TAttnArgs& a, hipStream_t s);

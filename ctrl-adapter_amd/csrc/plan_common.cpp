@@ -82,14 +82,14 @@ int run_layernorm(Ctx& cx, const Norm& n, const TV& x, half_t* y, int M, int dim
 }
 
 int run_conv(Ctx& cx, const ConvW& c, const half_t* x, const TV& y, int N, int Hin, int Win, const ConvOpts& o) {
-    const int k = c.taps == 9 ? 3 : 1, pad = c.taps == 9 ? 1 : 0;
-    const int Hout = (Hin * o.up + 2 * pad - k) / o.stride + 1, Wout = (Win * o.up + 2 * pad - k) / o.stride + 1;
+    const int k = c.taps == 9 ? 3 : 1, pads = c.taps == 9 ? (o.tap_origin ? 1 : 2) : 0;     // padding summed over both sides
+    const int Hout = (Hin * o.up + pads - k) / o.stride + 1, Wout = (Win * o.up + pads - k) / o.stride + 1;
     IGemmArgs g = {};
     // a 1x1 convolution at stride 1 is a row GEMM over the pixels: the rows form of the kernels skips the per-k-tile gather arithmetic
     // of the conv2d form (M32768 N320 K640 split operand: 40 us against 62 us in the round-5 profile); same arithmetic, same results
     const bool as_rows = c.taps == 1 && o.stride == 1 && o.up == 1 && o.res_up != 2;
     g.A = x; g.lda = o.lda ? o.lda : c.Cin; g.mode = as_rows ? IG_ROWS : IG_CONV2D; g.Cin = c.Cin; g.taps = c.taps;
-    g.Hin = Hin; g.Win = Win; g.Hout = Hout; g.Wout = Wout; g.stride = o.stride; g.up = o.up;
+    g.Hin = Hin; g.Win = Win; g.Hout = Hout; g.Wout = Wout; g.stride = o.stride; g.up = o.up; g.tap_origin = o.tap_origin;
     g.W = c.w; g.M = N * Hout * Wout; g.Nout = c.Cout; g.Ktot = c.taps * c.Cin;
     g.bias = c.b; g.rowvec = o.rowvec; g.rowvec_ld = o.rowvec_ld; g.rows_per_img = Hout * Wout;
     g.scale = 1.f; g.act = o.act; g.a_split = c.paired ? 2 : (c.dup ? 1 : 0);

@@ -568,6 +568,7 @@ struct ConvOpts {
     TV res;
     int res_up = 0;            // 2: res is the half-resolution map, read through a nearest x2 up-sampling (ctrl_igemm_desc::res_up)
     int act = 0;
+    int tap_origin = 0;        // 1: a 3x3 conv whose taps start at stride*o -- Downsample2D(padding=0) (ctrl_igemm_desc::tap_origin)
 };
 int run_conv(Ctx& cx, const ConvW& c, const half_t* x, const TV& y, int N, int Hin, int Win, const ConvOpts& o);
 // rowvec (optional): fp32 [M / rows_per_vec][rowvec_ld] added to every row of its group by the GEMM epilogue

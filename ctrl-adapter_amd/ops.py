@@ -58,14 +58,14 @@ def pack_vec(v, geglu=False):
 def igemm(A, lda, W, M, Nout, Cin, taps=1, mode=IG_ROWS, geom=None, bias=None, rowvec=None, rows_per_img=1,
           res=None, ldres=0, scale=1.0, geglu=False, segs=None, F=0, HW=0, out16=None, ld16=0, splitk_ws=None,
           blend_mix=None, blend_x=None, ld_blend=0, a_split=False, out16_lo_off=0, t_pad=False, scale2=0.0, scale2_from=0,
-          res_up=0, scale2_to=0):
+          res_up=0, scale2_to=0, tap_origin=0):
     """segs: list of (out_tensor, ld, col_begin, ncols, fmt, L); res_up=2: `res` is [N][Hout/2][Wout/2][ldres], read through a
     nearest x2 up-sampling (conv2d)"""
     d = L.IGemmDesc()
     d.A = A.data_ptr(); d.lda = lda; d.mode = mode; d.Cin = Cin; d.taps = taps
     g = geom or {}
     d.Hin = g.get("Hin", 1); d.Win = g.get("Win", 1); d.Hout = g.get("Hout", 1); d.Wout = g.get("Wout", 1)
-    d.stride = g.get("stride", 1); d.up = g.get("up", 1)
+    d.stride = g.get("stride", 1); d.up = g.get("up", 1); d.tap_origin = tap_origin
     d.F = F; d.HW = HW; d.t_pad = int(t_pad)
     d.W = W.data_ptr(); d.M = M; d.Nout = Nout; d.Ktot = taps * Cin
     d.bias = bias.data_ptr() if bias is not None else None

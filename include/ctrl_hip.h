@@ -79,7 +79,9 @@ typedef struct ctrl_igemm_desc {
     int32_t t_pad;      /* temporal, frame-sharded clip: A = padded [clip][F+2][HW][lda] (slots 0 / F+1 = halo frames), M rows = the F local frames */
     const void* W;      /* fp16 [Nout][taps*Cin] */
     int32_t M, Nout, Ktot;
-    int32_t pad1_;
+    int32_t tap_origin; /* conv2d 3x3: 0 = taps at stride*o - 1 .. stride*o + 1 (padding 1 on every side); 1 = taps at stride*o ..
+                           stride*o + 2 (no padding before the map, zeros past its end: diffusers' Downsample2D(padding=0) after
+                           F.pad(x, (0, 1, 0, 1))) */
     const float* bias;  /* [Nout] or NULL */
     const float* rowvec; int32_t rowvec_ld; int32_t rows_per_img;   /* + rowvec[(m/rows_per_img)*ld + n] */
     const void* res; int64_t ldres;                                 /* + res[m*ldres + n] (fp16, or fp32 if res_f32) */
@@ -579,6 +581,40 @@ int ctrl_op_vision_cls_ln(const float* x, int N, int L, int C, const float* gamm
                           int out_dtype, float* pooled32, void* stream);
 int ctrl_op_clip_resize_aa(const void* src, int src_dtype, int N, int H, int W, int OH, int OW, const float* mean_std, void* out,
                            int out_dtype, void* stream);
+
+/* ---- KL-VAE encoder (diffusers AutoencoderKL / AutoencoderKLTemporalDecoder: Encoder + quant_conv + DiagonalGaussianDistribution;
+ * the image latents of the SVD pipeline's _encode_vae_image and I2VGen-XL's prepare_image_latents) ---- */
+typedef struct ctrl_vae_encoder_config {
+    int32_t num_levels;              /* len(block_out_channels), 1..4 */
+    int32_t block_out_channels[4];   /* multiples of 32, <= 2048 */
+    int32_t layers_per_block;
+    int32_t latent_channels;         /* 1..8 */
+    int32_t norm_num_groups;         /* 32 */
+    float norm_eps;                  /* 1e-6 */
+} ctrl_vae_encoder_config;
+typedef struct ctrl_vae_encoder ctrl_vae_encoder;   /* opaque */
+/* parameters: diffusers' keys (encoder.conv_in.*, encoder.down_blocks.{i}.resnets.{j}.*, ..., quant_conv.*) */
+int ctrl_vae_encoder_param_count(const ctrl_vae_encoder_config* cfg);
+int ctrl_vae_encoder_param_spec(const ctrl_vae_encoder_config* cfg, int i, char* name, int name_len, int64_t shape[6], int* ndim);
+int ctrl_vae_encoder_create(const ctrl_vae_encoder_config* cfg, const ctrl_tensor_ref* tensors, int n_tensors, void* stream,
+                            ctrl_vae_encoder** out);
+void ctrl_vae_encoder_destroy(ctrl_vae_encoder* h);
+/* output kinds of the forward and of ctrl_op_vae_posterior; the latent grid is h x w = H / 2^(num_levels-1) x W / 2^(num_levels-1) */
+enum { CTRL_VAE_MODE = 0,       /* out [N][lat][h][w] = mean * scale */
+       CTRL_VAE_SAMPLE = 1,     /* out [N][lat][h][w] = (mean + std * eps) * scale, eps [N][lat][h][w] in eps_dtype */
+       CTRL_VAE_MOMENTS = 2 };  /* out [N][4*lat][h][w] = mean | logvar | std | var (logvar clamped to [-30, 20]; scale ignored) */
+/* pixels [N][3][H][W] (CTRL_F32 / F16 / BF16) in device memory, H and W multiples of 2^(num_levels-1) and of 8.  An image's result
+   is bit-identical whatever batch it is encoded in.  The first forward of a larger shape allocates the workspace (not under stream
+   capture); every later one is capturable. */
+int ctrl_vae_encoder_forward(ctrl_vae_encoder* h, const void* pixels, int pixel_dtype, int N, int H, int W, const void* eps,
+                             int eps_dtype, float scale, int kind, void* out, int out_dtype, void* stream);
+/* op level (csrc/vae.hip).  row_softmax: P[r][c] (fp16, row stride ldp) = softmax_c(S[r][c]) over c < L in fp32 (S row stride lds),
+   P[r][c] = 0 for L <= c < Lpad.  posterior: x fp32 NHWC rows [N*h*w][ldx] (x_nchw = 0: the conv_out result) or NCHW planes
+   [N][ldx][h][w] (x_nchw = 1: a MOMENTS output), first 2*lat channels read; wq fp32 [2*lat][2*lat] / bq [2*lat] = quant_conv (NULL: none);
+   then as the forward's kinds above. */
+int ctrl_op_vae_row_softmax(const float* S, int64_t lds, void* P, int64_t ldp, int rows, int L, int Lpad, void* stream);
+int ctrl_op_vae_posterior(const float* x, int64_t ldx, int x_nchw, const float* wq, const float* bq, int N, int lat, int h, int w,
+                          const void* eps, int eps_dtype, float scale, int kind, void* out, int out_dtype, void* stream);
 
 /* ---- Router (model/ctrl_router.py) ---- */
 /* weights_out fp32 device [num_routers + (has_mid?1:0)][E]; wg fp32 device same shape (Linear(1,E).weight[:,0]
