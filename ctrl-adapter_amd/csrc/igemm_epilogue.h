@@ -421,6 +421,7 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmArgs& e, f4 (&acc)[BM 
             const int pcb = n0 + wn * WN + ni * 16;      // packed column block start
             if (pcb >= e.Nout) continue;
             const int pcol = pcb + ecol;                 // packed column (bias index)
+            if (pcol >= e.Nout) continue;                // Nout % 16 != 0: the last fragment is partly outside the problem (per lane)
             const int ocol = e.geglu ? ((pcb >> 5) << 4) + ecol : pcol;   // output column
             const int ocb = ocol - ecol;
             // segment lookup (segment boundaries are multiples of 16 -> uniform per fragment)

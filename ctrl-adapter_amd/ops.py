@@ -58,9 +58,27 @@ def pack_vec(v, geglu=False):
 def igemm(A, lda, W, M, Nout, Cin, taps=1, mode=IG_ROWS, geom=None, bias=None, rowvec=None, rows_per_img=1,
           res=None, ldres=0, scale=1.0, geglu=False, segs=None, F=0, HW=0, out16=None, ld16=0, splitk_ws=None,
           blend_mix=None, blend_x=None, ld_blend=0, a_split=False, out16_lo_off=0, t_pad=False, scale2=0.0, scale2_from=0,
-          res_up=0, scale2_to=0, tap_origin=0):
+          res_up=0, scale2_to=0, tap_origin=0, pinned=False, splitk_tickets=None):
     """segs: list of (out_tensor, ld, col_begin, ncols, fmt, L); res_up=2: `res` is [N][Hout/2][Wout/2][ldres], read through a
-    nearest x2 up-sampling (conv2d)"""
+    nearest x2 up-sampling (conv2d); pinned: the encoder plans' fixed 64 x 64 x 64 form (op_igemm_pinned) instead of the dispatcher;
+    splitk_tickets: zeroed int32 ticket words of the in-launch split-K reduction (None: the library zeroes its own)"""
+    d = igemm_desc(**{k: v for k, v in locals().items() if k != "pinned"})
+    L.check((L.lib().ctrl_op_igemm_pinned if pinned else L.lib().ctrl_op_igemm)(C.byref(d), L.cur_stream()))
+
+
+def igemm_splitk_plan(d):
+    """(splits, scratch bytes, ticket words) ctrl_op_igemm would use for the descriptor `d` (igemm_desc) given a split-K scratch: the
+    descriptor must already carry a non-null, aligned splitk_ws (the choice depends on pointer alignment), of any size"""
+    lib = L.lib()
+    sk = lib.ctrl_igemm_splitk_factor(C.byref(d))
+    return sk, int(lib.ctrl_igemm_splitk_ws_bytes(C.byref(d), sk)), int(lib.ctrl_igemm_splitk_ticket_words(C.byref(d), sk))
+
+
+def igemm_desc(A, lda, W, M, Nout, Cin, taps=1, mode=IG_ROWS, geom=None, bias=None, rowvec=None, rows_per_img=1,
+               res=None, ldres=0, scale=1.0, geglu=False, segs=None, F=0, HW=0, out16=None, ld16=0, splitk_ws=None,
+               blend_mix=None, blend_x=None, ld_blend=0, a_split=False, out16_lo_off=0, t_pad=False, scale2=0.0, scale2_from=0,
+               res_up=0, scale2_to=0, tap_origin=0, splitk_tickets=None):
+    """the ctrl_igemm_desc of ops.igemm's arguments (the tensors must stay alive while it is used)"""
     d = L.IGemmDesc()
     d.A = A.data_ptr(); d.lda = lda; d.mode = mode; d.Cin = Cin; d.taps = taps
     g = geom or {}
@@ -79,6 +97,7 @@ def igemm(A, lda, W, M, Nout, Cin, taps=1, mode=IG_ROWS, geom=None, bias=None, r
     d.out16 = out16.data_ptr() if out16 is not None else None
     d.splitk_ws = splitk_ws.data_ptr() if splitk_ws is not None else None
     d.splitk_ws_bytes = splitk_ws.numel() * splitk_ws.element_size() if splitk_ws is not None else 0
+    d.splitk_tickets = splitk_tickets.data_ptr() if splitk_tickets is not None else None
     d.ld16 = ld16
     d.blend_mix = blend_mix.data_ptr() if blend_mix is not None else None
     d.blend_x = blend_x.data_ptr() if blend_x is not None else None
@@ -91,7 +110,7 @@ def igemm(A, lda, W, M, Nout, Cin, taps=1, mode=IG_ROWS, geom=None, bias=None, r
     for i, (out, ld, cb, nc, fmt, Ltok) in enumerate(segs):
         d.seg[i].out = out.data_ptr(); d.seg[i].ld = ld; d.seg[i].col_begin = cb; d.seg[i].ncols = nc
         d.seg[i].fmt = fmt; d.seg[i].dtype = L.dtype_code(out.dtype); d.seg[i].L = Ltok
-    L.check(L.lib().ctrl_op_igemm(C.byref(d), L.cur_stream()))
+    return d
 
 
 def ffn_pack_w2(w2_packed):

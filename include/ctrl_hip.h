@@ -121,6 +121,15 @@ typedef struct ctrl_igemm_desc {
                             (ctrl_range_check / CTRL_CHECK_FINITE=1) */
 } ctrl_igemm_desc;
 int ctrl_op_igemm(const ctrl_igemm_desc* d, void* stream);
+/* Test ABI.  The pinned form of the encoder plans: the 64 x 64 x 64 tile at every M, never split-K (row-major problems with
+   Cin % 64 == 0 on the aligned vector epilogue; anything else is refused). */
+int ctrl_op_igemm_pinned(const ctrl_igemm_desc* d, void* stream);
+/* Test ABI.  What ctrl_op_igemm would do with the descriptor's split-K scratch: the number of K splits (1 = none; depends on the
+   descriptor's pointers and strides and on ctrl_igemm_set_wide), and the exact sizes of the scratch (bytes) and of the zeroed
+   ticket words (int32 words; 0 = the in-launch reduction does not apply) for that many splits. */
+int ctrl_igemm_splitk_factor(const ctrl_igemm_desc* d);
+int64_t ctrl_igemm_splitk_ws_bytes(const ctrl_igemm_desc* d, int splits);
+int64_t ctrl_igemm_splitk_ticket_words(const ctrl_igemm_desc* d, int splits);
 /* Fused GEGLU feed-forward of a transformer block with dim 512 / hidden 2048 (csrc/ffn.hip; diffusers FeedForward(GEGLU) under
    BasicTransformerBlock / TemporalBasicTransformerBlock, model/adapter_spatial_temporal.py:108-130):
        out = epilogue( ((X W1h^T + b1h) * gelu_erf(X W1g^T + b1g)) W2^T )

@@ -33,3 +33,118 @@ def check_digest(t, d, tol, what=""):
         err = max(err, ((t - full).abs().max().item()) / max(full.abs().max().item(), 1e-12))
         assert err <= tol, "%s: rel_inf over the full tensor %.3e > %.1e" % (what, err, tol)
     return err
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Element-wise check of an implicit-GEMM result (tests/test_gpu_igemm_forms.py; self-test: tests/test_igemm_check_host.py)
+#
+#   out = scale * (A . W^T + bias + rowvec + res),  fp16 operands, fp32 accumulation, compared with an fp64 reference:
+#
+#   |out - ref| <= (Ktot + 8) * 2^-24 * (|A| . |W|^T + |bias| + |rowvec| + |res|) * max(1, |scale|)
+#                  + [fp16 output] 2^-11 * |ref| + 2^-25
+#                  + [bf16 output] 2^-8 * |ref|
+#
+# The first term bounds a length-Ktot fp32 sum in ANY order (+ 8: the epilogue's few extra operations); the others are one
+# round-to-nearest of the result (2^-25: half the smallest fp16 subnormal).  Nothing in it is measured; there is no slack factor.
+# ---------------------------------------------------------------------------------------------------------------------
+IGEMM_REL_INF_TOL = 2e-3          # the suite's per-tensor tolerance (tests/test_gpu_ops.py), asserted beside the bound
+IGEMM_REL_INF_TOL_BF16 = 1e-2     # (one bf16 rounding alone is 3.9e-3: the suite's bf16 tolerance)
+
+
+def igemm_bound(ref, mag, ktot, scale, out_dtype):
+    """the element-wise bound above; ref / mag fp64 tensors, scale a float or a per-column fp64 tensor"""
+    s = scale.abs().clamp_min(1.0) if torch.is_tensor(scale) else max(1.0, abs(float(scale)))
+    b = (ktot + 8) * 2.0 ** -24 * mag.double() * s
+    if out_dtype == torch.float16:
+        b = b + 2.0 ** -11 * ref.abs() + 2.0 ** -25
+    elif out_dtype == torch.bfloat16:
+        b = b + 2.0 ** -8 * ref.abs()
+    else:
+        assert out_dtype == torch.float32, out_dtype
+    return b
+
+
+def assert_igemm_close(out, ref, mag, ktot, scale, what="", extra=None, out_dtype=None):
+    """every element of `out` within igemm_bound of the fp64 `ref`, AND the per-tensor rel_inf within the suite's tolerance;
+    `extra`: an fp64 tensor added to the bound (a derived term of the caller's, e.g. the lo half of a split mirror); `out_dtype`: the
+    format the values were rounded to, when `out` itself is a wider copy.
+    Returns (worst |err| / bound, rel_inf)."""
+    o = out.detach().cpu()
+    dt = out_dtype or o.dtype
+    o = o.double()
+    ref = ref.double()
+    assert o.shape == ref.shape, (what, tuple(o.shape), tuple(ref.shape))
+    assert bool(torch.isfinite(o).all()), "%s: %d non-finite outputs (a poisoned pad reached a kept element); first at %s" % (
+        what, int((~torch.isfinite(o)).sum()), tuple(int(v) for v in (~torch.isfinite(o)).nonzero()[0]))
+    bound = igemm_bound(ref, mag, ktot, scale, dt)
+    if extra is not None:
+        bound = bound + extra
+    err = (o - ref).abs()
+    ratio = err / bound
+    worst = float(ratio.max())
+    rel = float(err.max() / ref.abs().max().clamp_min(1e-12))
+    print("IGEMM-CHECK %-70s worst err/bound %.3f  rel_inf %.2e" % (what, worst, rel))
+    bad = err > bound
+    if bool(bad.any()):
+        idx = bad.nonzero()
+        first = tuple(int(v) for v in idx[0])
+        rows = sorted({int(v) for v in idx[:, 0]})
+        raise AssertionError("%s: %d of %d elements beyond the fp32-accumulation bound (worst err/bound %.2f); first at %s: got %.6g want %.6g "
+                             "bound %.3g; first-axis indices hit: %s%s" % (what, int(bad.sum()), bad.numel(), worst, first, float(o[first]),
+                                                                            float(ref[first]), float(bound[first]), rows[:12], " ..." if len(rows) > 12 else ""))
+    tol = IGEMM_REL_INF_TOL_BF16 if dt == torch.bfloat16 else IGEMM_REL_INF_TOL
+    assert rel <= tol, "%s: rel_inf %.3e > %.1e" % (what, rel, tol)
+    return worst, rel
+
+
+_POISON = {torch.float16: 1.2345e2, torch.float32: -7.6543e4, torch.bfloat16: 3.5e3, torch.int32: 0x5A5A5A5A}     # fixed, non-NaN
+
+
+def _bits(t):
+    t = t.detach().cpu().contiguous()
+    return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
+
+
+class Guarded:
+    """An operand or result that lives INSIDE a larger allocation.
+
+    Guarded.out(...)  : an output; the surroundings hold a fixed non-NaN bit pattern and must come back bit for bit.
+    Guarded.inp(...)  : an input; the surroundings hold NaN, so anything read from them that reaches a kept accumulator shows
+                        (the MFMA propagates NaN) -- and they must not be written either.
+    `valid` is a tuple of slices of the full buffer: .view is the tensor the kernel is given (its strides are the buffer's)."""
+
+    def __init__(self, full_shape, valid, dtype, device, fill):
+        self.buf = torch.full(tuple(full_shape), fill, dtype=dtype, device=device)
+        self.valid = tuple(valid)
+        self.view = self.buf[self.valid]
+        self.is_input = False
+        self._snap = None
+
+    @classmethod
+    def out(cls, full_shape, valid, dtype, device):
+        g = cls(full_shape, valid, dtype, device, _POISON[dtype])
+        g._snap = _bits(g.buf).clone()
+        return g
+
+    @classmethod
+    def inp(cls, data, before, after, device, fill=float("nan")):
+        """`data` placed at offset `before` inside a buffer that extends `after` past it (per axis), the rest = fill"""
+        full = [b + s + a for b, s, a in zip(before, data.shape, after)]
+        valid = tuple(slice(b, b + s) for b, s in zip(before, data.shape))
+        g = cls(full, valid, data.dtype, device, fill)
+        g.view.copy_(data)
+        g.is_input = True
+        g._snap = _bits(g.buf).clone()
+        return g
+
+    def assert_untouched(self, what=""):
+        """everything outside .view is bit for bit what it was (for an input: the view too)"""
+        now, snap = _bits(self.buf), self._snap
+        diff = now != snap
+        if not self.is_input:
+            diff[self.valid] = False
+        if bool(diff.any()):
+            idx = diff.nonzero()
+            raise AssertionError("%s: %d element(s) outside the problem were written; first at buffer index %s (valid region %s of %s)" % (
+                what, int(diff.sum()), tuple(int(v) for v in idx[0]), [(s.start, s.stop) for s in self.valid], tuple(self.buf.shape)))
+
