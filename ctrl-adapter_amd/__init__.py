@@ -10,3 +10,4 @@ from .text_encoder import CLIPTextModel, CLIPTextOutput, encode_controlnet_promp
 from .text_encoder import CLIPTextModelWithProjection, CLIPTextModelOutput, encode_sdxl_prompt  # noqa: F401
 from .vision_encoder import CLIPVisionModelWithProjection, CLIPVisionModelOutput, encode_i2vgen_image, encode_svd_image  # noqa: F401
 from .vae_encoder import AutoencoderKLEncoder, encode_svd_image_latents, prepare_i2vgen_image_latents  # noqa: F401
+from .vae_decoder import AutoencoderKL, AutoencoderKLDecoder, DecoderOutput, decode_i2vgen_latents, decode_sdxl_latents  # noqa: F401

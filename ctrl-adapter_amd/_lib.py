@@ -98,6 +98,14 @@ class VaeEncoderConfig(C.Structure):
 VAE_MODE, VAE_SAMPLE, VAE_MOMENTS = 0, 1, 2      # output kinds of ctrl_vae_encoder_forward / ctrl_op_vae_posterior
 
 
+class VaeDecoderConfig(C.Structure):
+    _fields_ = [("num_levels", C.c_int32), ("block_out_channels", C.c_int32 * 4), ("layers_per_block", C.c_int32),
+                ("latent_channels", C.c_int32), ("norm_num_groups", C.c_int32), ("norm_eps", C.c_float), ("out_channels", C.c_int32)]
+
+
+VAE_DEC_SAMPLE, VAE_DEC_UNIT, VAE_DEC_U8 = 0, 1, 2      # epilogues of ctrl_vae_decoder_forward / ctrl_op_vae_dec_tail
+
+
 U8_NHWC = 3     # pixel dtype of ctrl_vision_encoder_forward / the vision ops: uint8 [N][H][W][3]
 
 
@@ -137,6 +145,8 @@ EXPORTS = [
     "ctrl_vision_encoder_forward", "ctrl_op_vision_patchify", "ctrl_op_vision_embed", "ctrl_op_vision_cls_ln", "ctrl_op_clip_resize_aa",
     "ctrl_vae_encoder_param_count", "ctrl_vae_encoder_param_spec", "ctrl_vae_encoder_create", "ctrl_vae_encoder_destroy",
     "ctrl_vae_encoder_forward", "ctrl_op_vae_row_softmax", "ctrl_op_vae_posterior",
+    "ctrl_vae_decoder_param_count", "ctrl_vae_decoder_param_spec", "ctrl_vae_decoder_create", "ctrl_vae_decoder_destroy",
+    "ctrl_vae_decoder_forward", "ctrl_vae_decoder_forward_strided", "ctrl_op_vae_dec_head", "ctrl_op_vae_dec_tail",
 ]
 
 _lib = None
@@ -155,7 +165,7 @@ def lib():
         for name in EXPORTS:
             fn = getattr(_lib, name)
             if name not in ("ctrl_last_error", "ctrl_policy_get", "ctrl_policy_name", "ctrl_controlnet_destroy", "ctrl_adapter_destroy", "ctrl_rccl_comm_destroy", "ctrl_rccl_comm_bytes_sent",
-                            "ctrl_text_encoder_destroy", "ctrl_vision_encoder_destroy", "ctrl_vae_encoder_destroy"):
+                            "ctrl_text_encoder_destroy", "ctrl_vision_encoder_destroy", "ctrl_vae_encoder_destroy", "ctrl_vae_decoder_destroy"):
                 fn.restype = C.c_int
         _lib.ctrl_policy_get.restype = C.c_char_p
         _lib.ctrl_policy_get.argtypes = [C.c_char_p]
@@ -196,6 +206,16 @@ def lib():
         _lib.ctrl_op_vae_row_softmax.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]
         _lib.ctrl_op_vae_posterior.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                                C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        _lib.ctrl_vae_decoder_destroy.restype = None
+        _lib.ctrl_vae_decoder_destroy.argtypes = [C.c_void_p]
+        _lib.ctrl_vae_decoder_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
+                                                  C.c_void_p, C.c_int, C.c_void_p]
+        _lib.ctrl_vae_decoder_forward_strided.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
+                                                          C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        _lib.ctrl_op_vae_dec_head.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p]
+        _lib.ctrl_op_vae_dec_tail.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int,
+                                              C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         _lib.ctrl_rccl_comm_destroy.restype = None
         _lib.ctrl_rccl_comm_destroy.argtypes = [C.c_void_p]
         _lib.ctrl_rccl_comm_bytes_sent.restype = C.c_int64

@@ -153,6 +153,16 @@ int op_vae_row_softmax(const float* S, long lds, half_t* P, long ldp, int rows, 
 int op_vae_posterior(const float* x, long ldx, int x_nchw, const float* wq, const float* bq, int N, int lat, int h, int w, const void* eps,
                      int eps_dt, float scale, int kind, void* out, int out_dt, hipStream_t s);
 
+// KL-VAE decoder (vae.hip), one image per call.  Head: NCHW latents [lat][h][w] (dt, ch_stride elements between its dense [h][w] channel
+// planes) * scale -> post_quant_conv (wpq fp32 [lat][lat] +
+// bpq) -> conv_in 3x3 (w fp32 [9][lat][Cout], op_pack_conv_w_direct) in fp32 -> fp32 NHWC [h*w][Cout].  Tail: fp32 NHWC stream [H*W][C]
+// -> conv_norm_out (stats: the sums of op_gn_stats over x) + SiLU -> conv_out 3x3 (w fp32 [9][C][Cout], Cout <= 4) on the VALU in fp32
+// -> the epilogue `kind` (include/ctrl_hip.h: CTRL_VAE_DEC_*)
+int op_vae_dec_head(const void* z, int dt, float scale, const float* wpq, const float* bpq, const float* w, const float* b, float* out,
+                    int lat, int h, int wd, long ch_stride, int Cout, hipStream_t s);
+int op_vae_dec_tail(const float* x, const float* stats, const float* gamma, const float* beta, float eps, const float* w, const float* b,
+                    int H, int W, int C, int Cout, int kind, void* out, int out_dt, hipStream_t s);
+
 // temporal attention over the frame axis: tokens X [(b*F+f)*HW + p][...]; seq = F (<= 32)
 typedef ctrl_tattn_desc TAttnArgs;
 int op_temporal_attn(const TAttnArgs& a, hipStream_t s);

@@ -2,6 +2,8 @@
 // (sequence of HIP kernel launches) used by both orchestrators.  Names of leaf modules follow
 // diffusers v0.27.x (SURVEY.md section 8b "Weights / persistence").
 #include "plan_common.h"
+#include <algorithm>
+#include <cmath>
 
 // ------------------------------------------------------------------------------------------ builders
 int build_resnet(ParamSink& ps, const std::string& pre, int Cin, int Cout, bool force_shortcut, ResnetW* w, bool dup, int dup_shortcut) {
@@ -378,6 +380,78 @@ int run_basic_tb(Ctx& cx, const BasicTBW& w, const TV& X, const TV& out, int B, 
         TRY(run_cross_attn(cx, w.attn2, w.norm2, x1, dim, x2, B, L, e, kv_pre, xn2, &w.norm3, xn3));
         TRY(run_ff(cx, w.norm3, w.ff1, w.ff2, x2, dim, out, M, xn3));
     }
+    cx.release(mk);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ KL-VAE mid-block attention
+static constexpr size_t kAttnCap = 256u << 20;     // bytes of the S (fp32) + P (fp16) chunk of the mid-block attention
+
+// a GEMM with the split-K scratch and tickets the dispatcher asks for (carved from the stack, as run_conv does)
+static int run_gemm(Ctx& cx, IGemmArgs g) {
+    const size_t mk = cx.mark();
+    const int sk = igemm_splitk_factor(g);
+    if (sk > 1) {
+        g.splitk_ws_bytes = (int64_t)igemm_splitk_ws_bytes(g, sk);
+        g.splitk_ws = cx.alloc((size_t)g.splitk_ws_bytes);
+        const size_t tw = igemm_splitk_ticket_words(g, sk);
+        if (tw) g.splitk_tickets = (int32_t*)cx.stats(tw);
+    }
+    RUN(cx, op_igemm(g, cx.s));
+    cx.release(mk);
+    return 0;
+}
+
+static IGemmArgs rows_gemm(const half_t* A, long lda, const half_t* W, int M, int Nout, int K, float scale) {
+    IGemmArgs g = {};
+    g.A = A; g.lda = lda; g.mode = IG_ROWS; g.Cin = K; g.taps = 1;
+    g.W = W; g.M = M; g.Nout = Nout; g.Ktot = K; g.scale = scale;
+    g.nseg = 1;
+    return g;
+}
+
+static int attn_chunk_rows(int L) {
+    const size_t Lpad = ((size_t)L + 63) / 64 * 64;
+    size_t r = kAttnCap / (L * 4 + Lpad * 2);
+    r = r >= 256 ? r / 256 * 256 : std::max<size_t>(64, r / 64 * 64);
+    return (int)std::min<size_t>(r, (size_t)L);
+}
+
+// mid-block attention of the KL-VAE plans (plan_common.h)
+int run_vae_mid_attention(Ctx& cx, const Norm& gn, const Lin& qkv, const Lin& to_out, int C, float eps, const TV& x, const TV& out, int L) {
+    const int Lpad = (L + 63) / 64 * 64, R = attn_chunk_rows(L);
+    const size_t mk = cx.mark();
+    half_t* h16 = cx.h((size_t)L * C);
+    TRY(run_groupnorm(cx, gn, x, h16, 1, L, eps, false));
+    half_t* q = cx.h((size_t)L * C);
+    half_t* k = cx.h((size_t)L * C);
+    half_t* v = cx.h((size_t)L * C);
+    half_t* vt = cx.h((size_t)C * Lpad);
+    half_t* ao = cx.h((size_t)L * C);
+    float* S = cx.f((size_t)R * L);
+    half_t* P = cx.h((size_t)R * Lpad);
+    {
+        IGemmArgs g = rows_gemm(h16, C, qkv.w, L, 3 * C, C, 1.f);
+        g.bias = qkv.b;
+        g.nseg = 3;
+        g.seg[0] = IGemmSeg{q, C, 0, C, SEG_ROW, DT_F16, 1, 0, nullptr};
+        g.seg[1] = IGemmSeg{k, C, C, C, SEG_ROW, DT_F16, 1, 0, nullptr};
+        g.seg[2] = IGemmSeg{v, C, 2 * C, C, SEG_ROW, DT_F16, 1, 0, nullptr};
+        TRY(run_gemm(cx, g));
+    }
+    RUN(cx, op_vision_vt(v, C, vt, 1, L, C, Lpad, cx.s));
+    const float scale = 1.0f / std::sqrt((float)C);
+    for (int r0 = 0; r0 < L; r0 += R) {
+        const int rows = std::min(R, L - r0);
+        IGemmArgs gs = rows_gemm(q + (size_t)r0 * C, C, k, rows, L, C, scale);
+        gs.seg[0] = IGemmSeg{S, L, 0, L, SEG_ROW, DT_F32, 1, 0, nullptr};
+        TRY(run_gemm(cx, gs));
+        RUN(cx, op_vae_row_softmax(S, L, P, Lpad, rows, L, Lpad, cx.s));
+        IGemmArgs gp = rows_gemm(P, Lpad, vt, rows, C, Lpad, 1.f);
+        gp.seg[0] = IGemmSeg{ao + (size_t)r0 * C, C, 0, C, SEG_ROW, DT_F16, 1, 0, nullptr};
+        TRY(run_gemm(cx, gp));
+    }
+    TRY(run_linear(cx, to_out, ao, C, out, C, L, x, C));
     cx.release(mk);
     return 0;
 }

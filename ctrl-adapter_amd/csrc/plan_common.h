@@ -583,6 +583,10 @@ int run_linear(Ctx& cx, const Lin& l, const half_t* x, long ldx, const TV& y, lo
 // x.m16 must exist when the block has a shortcut conv (it is that conv's operand).
 int run_resnet(Ctx& cx, const ResnetW& w, const TV& x, const TV& out, int N, int H, int W, int up,
                const float* temb_proj, int temb_ld, float eps);
+// Mid-block attention of the KL-VAE (diffusers Attention with its own GroupNorm, residual_connection, ONE head of dim C), shared by the
+// encoder and the decoder plans: out = to_out(softmax(Q K^T / sqrt(C)) V) + x over L tokens -- S = Q K^T on the GEMM in fp32, the row
+// softmax of vae.hip, O = P V against V^T, in query-row chunks whose S | P workspace stays under 256 MB
+int run_vae_mid_attention(Ctx& cx, const Norm& gn, const Lin& qkv, const Lin& to_out, int C, float eps, const TV& x, const TV& out, int L);
 // Encoder-hidden-state context prepared once per forward: fp16 copy [B*Lk][cross] (+ fp32 copy when Lk == 1)
 struct EhsCtx { const half_t* h16 = nullptr; const float* f32 = nullptr; int batch = 1, Lk = 0, cross = 0;
                 long row_ld = 0;   /* floats between the batch rows of f32 (0 = dense, Lk * cross) */ };

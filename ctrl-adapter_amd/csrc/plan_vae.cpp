@@ -4,7 +4,7 @@
 //   conv_in (direct 3 -> C0 conv on the NCHW pixels, any dtype, fp32 out) | per level: ResnetBlock2D x layers (no temb) + Downsample2D on all but
 //   the last level (F.pad(0, 1, 0, 1) + stride-2 3x3 conv = the implicit GEMM with tap_origin 1) | mid block: ResNet, attention (own
 //   GroupNorm; ONE head of dim C: S = Q K^T / sqrt(C) on the GEMM in fp32, the fp32 row softmax of vae.hip, O = P V on the GEMM, in
-//   query-row chunks whose S | P workspace stays under kAttnCap), to_out + residual, ResNet | conv_norm_out + SiLU | conv_out (weights
+//   query-row chunks whose S | P workspace stays under 256 MB: run_vae_mid_attention, plan_common.cpp), to_out + residual, ResNet | conv_norm_out + SiLU | conv_out (weights
 //   padded to 16 output rows) | the posterior kernel (quant_conv, clamp, mode / sample / moments).
 // The residual stream is fp32 from conv_in on.  Every convolution reads a split [hi | lo] fp16 operand (ctrl_igemm_desc::a_split): the
 // GroupNorm + SiLU outputs, and the stream's split mirror for the shortcut and downsample convolutions.  Plain fp16 operands measured
@@ -19,7 +19,6 @@
 
 namespace {
 
-constexpr size_t kAttnCap = 256u << 20;     // bytes of the S (fp32) + P (fp16) chunk of the mid-block attention
 constexpr int kConvOutRows = 16;            // conv_out's weight rows padded to one MFMA tile column block
 
 struct VaeLevel {
@@ -105,76 +104,6 @@ int pad_conv_out(VaeEncoder& t, hipStream_t s) {
     return 0;
 }
 
-// a GEMM with the split-K scratch and tickets the dispatcher asks for (carved from the stack, as run_conv does)
-int run_gemm(Ctx& cx, IGemmArgs g) {
-    const size_t mk = cx.mark();
-    const int sk = igemm_splitk_factor(g);
-    if (sk > 1) {
-        g.splitk_ws_bytes = (int64_t)igemm_splitk_ws_bytes(g, sk);
-        g.splitk_ws = cx.alloc((size_t)g.splitk_ws_bytes);
-        const size_t tw = igemm_splitk_ticket_words(g, sk);
-        if (tw) g.splitk_tickets = (int32_t*)cx.stats(tw);
-    }
-    RUN(cx, op_igemm(g, cx.s));
-    cx.release(mk);
-    return 0;
-}
-
-IGemmArgs rows_gemm(const half_t* A, long lda, const half_t* W, int M, int Nout, int K, float scale) {
-    IGemmArgs g = {};
-    g.A = A; g.lda = lda; g.mode = IG_ROWS; g.Cin = K; g.taps = 1;
-    g.W = W; g.M = M; g.Nout = Nout; g.Ktot = K; g.scale = scale;
-    g.nseg = 1;
-    return g;
-}
-
-int attn_chunk_rows(int L) {
-    const size_t Lpad = ((size_t)L + 63) / 64 * 64;
-    size_t r = kAttnCap / (L * 4 + Lpad * 2);
-    r = r >= 256 ? r / 256 * 256 : std::max<size_t>(64, r / 64 * 64);
-    return (int)std::min<size_t>(r, (size_t)L);
-}
-
-// mid-block attention (diffusers Attention, residual_connection, one head of dim C): out = to_out(softmax(Q K^T / sqrt(C)) V) + x
-int run_mid_attention(Ctx& cx, const VaeEncoder& t, const TV& x, const TV& out, int L) {
-    const int C = t.cfg.block_out_channels[t.cfg.num_levels - 1];
-    const int Lpad = (L + 63) / 64 * 64, R = attn_chunk_rows(L);
-    const size_t mk = cx.mark();
-    half_t* h16 = cx.h((size_t)L * C);
-    TRY(run_groupnorm(cx, t.attn_gn, x, h16, 1, L, t.cfg.norm_eps, false));
-    half_t* q = cx.h((size_t)L * C);
-    half_t* k = cx.h((size_t)L * C);
-    half_t* v = cx.h((size_t)L * C);
-    half_t* vt = cx.h((size_t)C * Lpad);
-    half_t* ao = cx.h((size_t)L * C);
-    float* S = cx.f((size_t)R * L);
-    half_t* P = cx.h((size_t)R * Lpad);
-    {
-        IGemmArgs g = rows_gemm(h16, C, t.qkv.w, L, 3 * C, C, 1.f);
-        g.bias = t.qkv.b;
-        g.nseg = 3;
-        g.seg[0] = IGemmSeg{q, C, 0, C, SEG_ROW, DT_F16, 1, 0, nullptr};
-        g.seg[1] = IGemmSeg{k, C, C, C, SEG_ROW, DT_F16, 1, 0, nullptr};
-        g.seg[2] = IGemmSeg{v, C, 2 * C, C, SEG_ROW, DT_F16, 1, 0, nullptr};
-        TRY(run_gemm(cx, g));
-    }
-    RUN(cx, op_vision_vt(v, C, vt, 1, L, C, Lpad, cx.s));
-    const float scale = 1.0f / std::sqrt((float)C);
-    for (int r0 = 0; r0 < L; r0 += R) {
-        const int rows = std::min(R, L - r0);
-        IGemmArgs gs = rows_gemm(q + (size_t)r0 * C, C, k, rows, L, C, scale);
-        gs.seg[0] = IGemmSeg{S, L, 0, L, SEG_ROW, DT_F32, 1, 0, nullptr};
-        TRY(run_gemm(cx, gs));
-        RUN(cx, op_vae_row_softmax(S, L, P, Lpad, rows, L, Lpad, cx.s));
-        IGemmArgs gp = rows_gemm(P, Lpad, vt, rows, C, Lpad, 1.f);
-        gp.seg[0] = IGemmSeg{ao + (size_t)r0 * C, C, 0, C, SEG_ROW, DT_F16, 1, 0, nullptr};
-        TRY(run_gemm(cx, gp));
-    }
-    TRY(run_linear(cx, t.attn_out, ao, C, out, C, L, x, C));
-    cx.release(mk);
-    return 0;
-}
-
 struct VaeFwd {
     const void* px; int pdt; int H, W;
     const void* eps; int eps_dt; float scale; int kind;
@@ -229,7 +158,7 @@ int run_image(Ctx& cx, const VaeEncoder& t, const VaeFwd& a, int n) {
     const int L = h * w;
     const int Ct = c.block_out_channels[nl - 1];
     { TV y = next(false, Ct); TRY(run_resnet(cx, t.mid0, x, y, 1, h, w, 1, nullptr, 0, eps)); x = y; }
-    { TV y = next(false, Ct); TRY(run_mid_attention(cx, t, x, y, L)); x = y; }
+    { TV y = next(false, Ct); TRY(run_vae_mid_attention(cx, t.attn_gn, t.qkv, t.attn_out, Ct, eps, x, y, L)); x = y; }
     { TV y = next(false, Ct); TRY(run_resnet(cx, t.mid1, x, y, 1, h, w, 1, nullptr, 0, eps)); x = y; }
     half_t* g16 = cx.h((size_t)L * 2 * Ct);
     TRY(run_groupnorm(cx, t.norm_out, x, g16, 1, L, eps, true, true));

@@ -7,6 +7,9 @@
 //                           the fp16 output of the shared direct kernel (smallconv.hip) alone put 6e-4 on the latents
 //   vae_posterior_kernel    conv_out rows -> quant_conv (1x1, fp32) -> DiagonalGaussianDistribution: mean | logvar clamped to
 //                           [-30, 20], std = exp(logvar / 2), var = exp(logvar) -> mode / sample / moments, NCHW
+// and of the decoder half (AutoencoderKL.decode; csrc/plan_vae_decoder.cpp):
+//   vae_dec_head_kernel     latents * scale -> post_quant_conv -> conv_in, all fp32, NCHW latents of any dtype -> the fp32 NHWC stream
+//   vae_dec_tail_kernel     conv_norm_out + SiLU + conv_out + the output epilogue (sample / [0, 1] / uint8) in one pass over the stream
 // Each computes a row or a pixel on its own: an image's results do not depend on the batch it is in.
 #include "ops.h"
 #include <math.h>
@@ -117,6 +120,133 @@ __global__ void __launch_bounds__(256) vae_posterior_kernel(const float* __restr
     }
 }
 
+// decoder head, one thread per (latent pixel, 16 output channels): for each of the 9 taps the lat latents of the tapped pixel * scale go
+// through post_quant_conv (fp32), zero outside the map (conv_in pads ITS input, the post_quant_conv result), then into the 16 sums.
+// cs: elements between the channel planes of z (H * W when dense; a frame of a [C][F][h][w] clip has F * h * w)
+__global__ void __launch_bounds__(256) vae_dec_head_kernel(const void* __restrict__ z, int dt, float scale, const float* __restrict__ wpq,
+                                                           const float* __restrict__ bpq, const float* __restrict__ w,
+                                                           const float* __restrict__ b, float* __restrict__ out, int lat, int H, int W,
+                                                           long cs, int Cout) {
+    const int groups = Cout / 16;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)H * W * groups) return;
+    const int pix = (int)(i / groups), c0 = (int)(i - (long)pix * groups) * 16;
+    const int y = pix / W, x = pix - y * W;
+    float acc[16];
+#pragma unroll
+    for (int c = 0; c < 16; ++c) acc[c] = b[c0 + c];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
+        if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
+        float v[kMaxLat];
+#pragma unroll
+        for (int ci = 0; ci < kMaxLat; ++ci) v[ci] = ci < lat ? load_as_f32(z, (size_t)ci * cs + (size_t)yy * W + xx, dt) * scale : 0.f;
+#pragma unroll
+        for (int o = 0; o < kMaxLat; ++o) {
+            if (o >= lat) break;
+            float q = bpq[o];
+#pragma unroll
+            for (int ci = 0; ci < kMaxLat; ++ci)
+                if (ci < lat) q = fmaf(wpq[o * lat + ci], v[ci], q);
+            const float* wr = w + ((size_t)t * lat + o) * Cout + c0;
+#pragma unroll
+            for (int c = 0; c < 16; ++c) acc[c] = fmaf(wr[c], q, acc[c]);
+        }
+    }
+    float4* o4 = (float4*)(out + (size_t)pix * Cout + c0);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) o4[c] = make_float4(acc[4 * c], acc[4 * c + 1], acc[4 * c + 2], acc[4 * c + 3]);
+}
+
+// decoder tail: conv_norm_out + SiLU + conv_out (C -> COUT <= 4, 3x3) + the output epilogue in ONE pass over the fp32 stream.  A
+// workgroup owns a kTailW x kTailH tile of output pixels (one per thread) and walks the channels in chunks of kTailCk: the chunk's halo
+// patch is staged in LDS already normalised and activated (zero outside the map: the convolution pads the ACTIVATED map), then every
+// thread adds its 9 taps x kTailCk channels into COUT fp32 sums; the weights are uniform across the workgroup (scalar loads).
+constexpr int kTailW = 32, kTailH = 8, kTailCk = 32;
+constexpr int kTailPs = kTailCk + 4;                                  // floats between the pixels of the patch (16-byte aligned, off the bank stride)
+constexpr int kTailPw = kTailW + 2, kTailPix = (kTailH + 2) * kTailPw;
+
+__device__ __forceinline__ float round_to_dt(float v, int dt) {
+    if (dt == DT_F16) return (float)(half_t)v;
+    if (dt == DT_BF16) return bf16_to_f32(f32_to_bf16(v));
+    return v;
+}
+
+template <int COUT>
+__global__ void __launch_bounds__(256) vae_dec_tail_kernel(const float* __restrict__ x, const float* __restrict__ stats,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                           const float* __restrict__ w, const float* __restrict__ b, int H, int W, int C,
+                                                           int kind, void* __restrict__ out, int out_dt) {
+    __shared__ __attribute__((aligned(16))) float patch[kTailPix * kTailPs];
+    __shared__ float sc[kTailCk], sf[kTailCk];     // the chunk's rstd * gamma and beta - mean * rstd * gamma
+    const int tid = threadIdx.x;
+    const int x0 = blockIdx.x * kTailW, y0 = blockIdx.y * kTailH;
+    const int cg = C / 32;
+    const float inv_cnt = 1.0f / ((float)H * (float)W * (float)cg);
+    const int lx = tid & (kTailW - 1), ly = tid / kTailW;
+    float acc[COUT];
+#pragma unroll
+    for (int o = 0; o < COUT; ++o) acc[o] = 0.f;
+    for (int c0 = 0; c0 < C; c0 += kTailCk) {
+        __syncthreads();                           // the previous chunk's patch and scales have been read
+        if (tid < kTailCk) {                       // the arithmetic of gn_apply_kernel (norm.hip)
+            const int c = c0 + tid, g = c / cg;
+            const float s = stats[g * 2], ss = stats[g * 2 + 1];
+            const float mean = s * inv_cnt;
+            const float var = fmaxf(ss * inv_cnt - mean * mean, 0.f);
+            const float rstd = rsqrtf(var + eps);
+            sc[tid] = rstd * gamma[c];
+            sf[tid] = beta[c] - mean * sc[tid];
+        }
+        __syncthreads();
+        for (int it = tid; it < kTailPix * (kTailCk / 4); it += 256) {
+            const int p = it / (kTailCk / 4), q = it - p * (kTailCk / 4);
+            const int py = p / kTailPw, px = p - py * kTailPw;
+            const int gy = y0 + py - 1, gx = x0 + px - 1;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
+                const int c = q * 4;
+                const float4 r = *(const float4*)(x + ((size_t)gy * W + gx) * C + c0 + c);
+                v.x = silu_f(fmaf(r.x, sc[c], sf[c]));
+                v.y = silu_f(fmaf(r.y, sc[c + 1], sf[c + 1]));
+                v.z = silu_f(fmaf(r.z, sc[c + 2], sf[c + 2]));
+                v.w = silu_f(fmaf(r.w, sc[c + 3], sf[c + 3]));
+            }
+            *(float4*)(patch + p * kTailPs + q * 4) = v;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const float* pp = patch + ((ly + t / 3) * kTailPw + lx + t % 3) * kTailPs;
+            const float* wt = w + ((size_t)t * C + c0) * COUT;
+#pragma unroll
+            for (int q = 0; q < kTailCk / 4; ++q) {
+                const float4 v = *(const float4*)(pp + q * 4);
+                const float vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int o = 0; o < COUT; ++o) acc[o] = fmaf(wt[(q * 4 + j) * COUT + o], vv[j], acc[o]);
+            }
+        }
+    }
+    const int gy = y0 + ly, gx = x0 + lx;
+    if (gy >= H || gx >= W) return;
+    const size_t hw = (size_t)H * W, pix = (size_t)gy * W + gx;
+#pragma unroll
+    for (int o = 0; o < COUT; ++o) {
+        const float v = round_to_dt(acc[o] + b[o], out_dt);       // what .sample holds in the module's dtype
+        if (kind == CTRL_VAE_DEC_SAMPLE) {
+            store_from_f32(out, (size_t)o * hw + pix, out_dt, v);
+        } else {
+            const float u = fminf(fmaxf(v * 0.5f + 0.5f, 0.f), 1.f);
+            if (kind == CTRL_VAE_DEC_UNIT) ((float*)out)[(size_t)o * hw + pix] = u;
+            else ((unsigned char*)out)[pix * COUT + o] = (unsigned char)rintf(u * 255.0f);      // rintf: ties to even, as numpy's round
+        }
+    }
+}
+
 }  // namespace
 
 int op_vae_row_softmax(const float* S, long lds, half_t* P, long ldp, int rows, int L, int Lpad, hipStream_t s) {
@@ -150,5 +280,40 @@ int op_vae_posterior(const float* x, long ldx, int x_nchw, const float* wq, cons
     PROF_WORK((double)n * (2.0 * 4 * lat * lat + 8.0 * lat), (double)n * (2 * lat * 4.0 + lat * (kind == CTRL_VAE_MOMENTS ? 16.0 : 4.0)));
     LAUNCH("vae_posterior", vae_posterior_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, ldx, x_nchw, wq, bq, N, lat, h * w,
            eps, eps_dt, scale, kind, out, out_dt);
+    return 0;
+}
+
+int op_vae_dec_head(const void* z, int dt, float scale, const float* wpq, const float* bpq, const float* w, const float* b, float* out,
+                    int lat, int h, int wd, long ch_stride, int Cout, hipStream_t s) {
+    CTRL_CHECK(z && wpq && bpq && w && b && out, "vae_dec_head: null argument");
+    CTRL_CHECK(lat >= 1 && lat <= kMaxLat && h >= 1 && wd >= 1 && Cout >= 16 && Cout % 16 == 0 && dt >= DT_F32 && dt <= DT_BF16 &&
+                   ((uintptr_t)out & 15) == 0,
+               "vae_dec_head: bad shape (1 <= latent channels <= 8, Cout % 16 == 0), dtype or alignment");
+    CTRL_CHECK(ch_stride >= (long)h * wd, "vae_dec_head: the channel stride must be at least h * w elements");
+    const long n = (long)h * wd * (Cout / 16);
+    CTRL_CHECK(n < (1L << 31), "vae_dec_head: too large");
+    PROF_WORK(2.0 * h * wd * (9.0 * lat * lat * (Cout / 16) + 9.0 * lat * Cout), (double)h * wd * (lat * 4.0 + Cout * 4.0));
+    LAUNCH("vae_dec_head", vae_dec_head_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, z, dt, scale, wpq, bpq, w, b, out, lat,
+           h, wd, ch_stride, Cout);
+    return 0;
+}
+
+int op_vae_dec_tail(const float* x, const float* stats, const float* gamma, const float* beta, float eps, const float* w, const float* b,
+                    int H, int W, int C, int Cout, int kind, void* out, int out_dt, hipStream_t s) {
+    CTRL_CHECK(x && stats && gamma && beta && w && b && out, "vae_dec_tail: null argument");
+    CTRL_CHECK(H >= 1 && W >= 1 && H <= 65535 * kTailH && W <= 65535 * kTailW && C >= 32 && C <= 2048 && C % 32 == 0 && Cout >= 1 && Cout <= 4 &&
+                   ((uintptr_t)x & 15) == 0,
+               "vae_dec_tail: bad shape (C a multiple of 32 up to 2048, 1 <= Cout <= 4) or alignment");
+    CTRL_CHECK(kind == CTRL_VAE_DEC_SAMPLE || kind == CTRL_VAE_DEC_UNIT || kind == CTRL_VAE_DEC_U8,
+               "vae_dec_tail: kind must be 0 sample, 1 unit or 2 u8");
+    CTRL_CHECK(out_dt >= DT_F32 && out_dt <= DT_BF16, "vae_dec_tail: bad dtype");
+    const dim3 grid((unsigned)((W + kTailW - 1) / kTailW), (unsigned)((H + kTailH - 1) / kTailH));
+    PROF_WORK(2.0 * 9 * H * W * (double)C * Cout, (double)H * W * (C * 4.0 + Cout * 4.0));
+    switch (Cout) {
+        case 1: LAUNCH("vae_dec_tail", vae_dec_tail_kernel<1>, grid, dim3(256), 0, s, x, stats, gamma, beta, eps, w, b, H, W, C, kind, out, out_dt); break;
+        case 2: LAUNCH("vae_dec_tail", vae_dec_tail_kernel<2>, grid, dim3(256), 0, s, x, stats, gamma, beta, eps, w, b, H, W, C, kind, out, out_dt); break;
+        case 3: LAUNCH("vae_dec_tail", vae_dec_tail_kernel<3>, grid, dim3(256), 0, s, x, stats, gamma, beta, eps, w, b, H, W, C, kind, out, out_dt); break;
+        default: LAUNCH("vae_dec_tail", vae_dec_tail_kernel<4>, grid, dim3(256), 0, s, x, stats, gamma, beta, eps, w, b, H, W, C, kind, out, out_dt); break;
+    }
     return 0;
 }

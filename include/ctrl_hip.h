@@ -625,6 +625,52 @@ int ctrl_op_vae_row_softmax(const float* S, int64_t lds, void* P, int64_t ldp, i
 int ctrl_op_vae_posterior(const float* x, int64_t ldx, int x_nchw, const float* wq, const float* bq, int N, int lat, int h, int w,
                           const void* eps, int eps_dtype, float scale, int kind, void* out, int out_dtype, void* stream);
 
+/* ---- KL-VAE decoder (diffusers AutoencoderKL.decode: post_quant_conv + Decoder; the image decode of the SDXL pipeline and the frame
+ * decode of I2VGen-XL's decode_latents) ---- */
+typedef struct ctrl_vae_decoder_config {
+    int32_t num_levels;              /* len(block_out_channels), 1..4 */
+    int32_t block_out_channels[4];   /* as in the VAE's config (the decoder walks them reversed); multiples of 32, <= 2048 */
+    int32_t layers_per_block;        /* every up block holds layers_per_block + 1 ResNets */
+    int32_t latent_channels;         /* 1..8 */
+    int32_t norm_num_groups;         /* 32 */
+    float norm_eps;                  /* 1e-6 */
+    int32_t out_channels;            /* 1..4 (3: RGB) */
+} ctrl_vae_decoder_config;
+typedef struct ctrl_vae_decoder ctrl_vae_decoder;   /* opaque */
+/* parameters: diffusers' keys (post_quant_conv.*, decoder.conv_in.*, decoder.mid_block.*, decoder.up_blocks.{i}.resnets.{j}.*,
+   decoder.up_blocks.{i}.upsamplers.0.conv.*, decoder.conv_norm_out.*, decoder.conv_out.*) */
+int ctrl_vae_decoder_param_count(const ctrl_vae_decoder_config* cfg);
+int ctrl_vae_decoder_param_spec(const ctrl_vae_decoder_config* cfg, int i, char* name, int name_len, int64_t shape[6], int* ndim);
+int ctrl_vae_decoder_create(const ctrl_vae_decoder_config* cfg, const ctrl_tensor_ref* tensors, int n_tensors, void* stream,
+                            ctrl_vae_decoder** out);
+void ctrl_vae_decoder_destroy(ctrl_vae_decoder* h);
+/* epilogues of the forward and of ctrl_op_vae_dec_tail; x = conv_out's fp32 result, rounded to out_dtype first (what .sample holds);
+   the image is H x W = h * 2^(num_levels-1) x w * 2^(num_levels-1) */
+enum { CTRL_VAE_DEC_SAMPLE = 0,   /* out [N][out_channels][H][W] in out_dtype = x: decode(z).sample */
+       CTRL_VAE_DEC_UNIT = 1,     /* out [N][out_channels][H][W] fp32 = clamp(x / 2 + 0.5, 0, 1): VaeImageProcessor.postprocess("pt") */
+       CTRL_VAE_DEC_U8 = 2 };     /* out [N][H][W][out_channels] uint8 = rint(clamp(x / 2 + 0.5, 0, 1) * 255), ties to even: numpy_to_pil */
+/* latents [N][latent_channels][h][w] (CTRL_F32 / F16 / BF16) in device memory, multiplied by `scale` (1 / scaling_factor) on load.  An
+   image's pixels are bit-identical whatever batch it is decoded in.  The first forward of a larger shape allocates the workspace (not
+   under stream capture); every later one is capturable. */
+int ctrl_vae_decoder_forward(ctrl_vae_decoder* h, const void* latents, int latent_dtype, int N, int lat_h, int lat_w, float scale, int kind,
+                             void* out, int out_dtype, void* stream);
+/* the same on latents that are not one dense block: image n starts image_stride elements after image n - 1 and its dense [h][w] channel
+   planes lie channel_stride (>= h * w) elements apart.  The F frames of clip b of [B][C][F][h][w] latents (I2VGen-XL's decode_latents)
+   are N = F images with image_stride = h * w and channel_stride = F * h * w: no permuted copy of the latents is needed. */
+int ctrl_vae_decoder_forward_strided(ctrl_vae_decoder* h, const void* latents, int latent_dtype, int N, int lat_h, int lat_w,
+                                     int64_t image_stride, int64_t channel_stride, float scale, int kind, void* out, int out_dtype,
+                                     void* stream);
+/* op level (csrc/vae.hip), one image each.  dec_head: z NCHW [lat][h][w] (z_dtype, ch_stride >= h * w elements between its channel
+   planes) * scale -> post_quant_conv (wpq fp32 [lat][lat],
+   bpq [lat]) -> conv_in 3x3 (w_in fp32 [9][lat][Cout] as ctrl_op_pack_conv_w_direct packs it, b_in [Cout]; Cout % 16 == 0), all fp32
+   -> out fp32 NHWC [h*w][Cout].  dec_tail: x fp32 NHWC [H*W][C] -> GroupNorm(32) from `stats` (ctrl_op_gn_stats of x: sum | sum of
+   squares per group) with gamma / beta, SiLU, conv_out 3x3 (w_out fp32 [9][C][Cout], b_out [Cout], Cout <= 4) in fp32 -> the epilogue
+   `kind` above. */
+int ctrl_op_vae_dec_head(const void* z, int z_dtype, float scale, const float* wpq, const float* bpq, const float* w_in, const float* b_in,
+                         float* out, int lat, int h, int w, int64_t ch_stride, int Cout, void* stream);
+int ctrl_op_vae_dec_tail(const float* x, const float* stats, const float* gamma, const float* beta, float eps, const float* w_out,
+                         const float* b_out, int H, int W, int C, int Cout, int kind, void* out, int out_dtype, void* stream);
+
 /* ---- Router (model/ctrl_router.py) ---- */
 /* weights_out fp32 device [num_routers + (has_mid?1:0)][E]; wg fp32 device same shape (Linear(1,E).weight[:,0]
  * per router; ignored for equal_weights); mask host int[E] (NULL = all ones). */
