@@ -126,6 +126,28 @@ class ParamTreeModule(PretrainedMixin, nn.Module):
         self._drop_plan()
         return super().load_state_dict(*a, **k)
 
+    # subclasses name their ctrl_*_create / ctrl_*_destroy exports and the attributes passed by reference ahead of the tensors
+    _CREATE = _DESTROY = None
+    _CREATE_CFG = ("_cfg",)
+
+    def _ensure_plan(self, slot="_plan", create=None, cfg=None):
+        """the plan in `slot`, created on first use from the module's parameters (a second plan over the same parameters names its
+        own slot, export and config attributes)"""
+        if getattr(self, slot) is None:
+            refs, n, keep = self._tensor_refs()
+            h = C.c_void_p()
+            cfgs = [C.byref(getattr(self, a)) for a in (cfg or self._CREATE_CFG)]
+            L.check(getattr(L.lib(), create or self._CREATE)(*cfgs, refs, n, L.cur_stream(), C.byref(h)))
+            setattr(self, slot, h)
+            self._plan_created(slot)
+        return getattr(self, slot)
+
+    def _plan_created(self, slot):
+        """hook: runs once after the plan in `slot` was created"""
+
+    def _destroy(self, plan):
+        getattr(L.lib(), self._DESTROY)(plan)
+
     def _drop_plan(self):
         if getattr(self, "_plan", None) is not None:
             self._destroy(self._plan)
@@ -214,6 +236,21 @@ class ParamTreeModule(PretrainedMixin, nn.Module):
     @property
     def device(self):
         return next(self.parameters()).device
+
+
+def _check_gpu_input(module, tensor, what, verb="lives"):
+    """the module's device, after the checks every `run` makes: the parameters and the input `what` (e.g. "the image") are on the GPU,
+    and on the same one"""
+    dev = module.device
+    if dev.type != "cuda":
+        raise RuntimeError("parameters must live on the GPU before the first forward (call .to('cuda')); there is no CPU path")
+    if not tensor.is_cuda:
+        raise RuntimeError("%s must live on the GPU; there is no CPU path" % what)
+    if tensor.device != dev:
+        raise ValueError("%s %s on %s, the model on %s" % (what, verb, tensor.device, dev))
+    return dev
+
+
 class Config(dict):
     """attribute-style access like diffusers' FrozenDict (pipelines read e.g. controlnet.config.global_pool_conditions)"""
 

@@ -20,6 +20,8 @@ class ControlNetOutput(tuple):
 
 
 class ControlNetModel(ParamTreeModule):
+    _CREATE, _DESTROY = "ctrl_controlnet_create", "ctrl_controlnet_destroy"
+
     def __init__(self, in_channels=4, conditioning_channels=3, flip_sin_to_cos=True, freq_shift=0,
                  down_block_types=("CrossAttnDownBlock2D", "CrossAttnDownBlock2D", "CrossAttnDownBlock2D", "DownBlock2D"),
                  mid_block_type="UNetMidBlock2DCrossAttn", only_cross_attention=False,
@@ -77,23 +79,14 @@ class ControlNetModel(ParamTreeModule):
     def config_dict(self):
         return {k: (list(v) if isinstance(v, tuple) else v) for k, v in self.config.items()}
 
-    def _destroy(self, plan):
-        L.lib().ctrl_controlnet_destroy(plan)
-
     def trim(self):
         """frees the workspace / cache blocks the plan outgrew (they are kept alive for queued launches and captured graphs);
         synchronises the device -- call between requests, when no graph captured before the last growth will be replayed"""
         if getattr(self, "_plan", None) is not None:
             L.check(L.lib().ctrl_controlnet_trim(self._plan))
 
-    def _ensure_plan(self):
-        if self._plan is None:
-            refs, n, keep = self._tensor_refs()
-            h = C.c_void_p()
-            L.check(L.lib().ctrl_controlnet_create(C.byref(self._cfg), refs, n, L.cur_stream(), C.byref(h)))
-            self._plan = h
-            self._note_selection(L.lib().ctrl_controlnet_selection)
-        return self._plan
+    def _plan_created(self, slot):
+        self._note_selection(L.lib().ctrl_controlnet_selection)
 
     def _drop_plan(self):
         self._cond_ref, self._cond_version, self._cond_key = None, -1, None      # the cache lives in the plan

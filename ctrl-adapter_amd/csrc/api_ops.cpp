@@ -1,7 +1,6 @@
 // extern "C" op-level entry points of libctrlhip (thin: validate, cast, forward to the op layer).
-#include "ops.h"
+#include "plan_shell.h"
 
-#define S(stream) ((hipStream_t)(stream))
 #define H(p) ((half_t*)(p))
 #define CH(p) ((const half_t*)(p))
 

@@ -134,7 +134,6 @@ struct AFwd {
 
 // ---- exchanges of the frame-sharded clip: every one lays its buffers out from offset 0 of the exchange workspace; reuse
 // is safe because everything (copies, transport calls, consumers) is ordered on the one stream the forward runs on ----
-inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline void ws_need(const AFwd& a, size_t bytes) { if (*a.ws_peak < bytes) *a.ws_peak = bytes; }
 #define COMM_TRY(expr) do { if ((expr) != 0) CTRL_FAIL("clip-sharded exchange failed: " #expr); } while (0)
 
@@ -597,7 +596,6 @@ struct AdapterCall {
     size_t* ws_peak;
 };
 
-size_t dt_size(int dt) { return dt == DT_F32 ? 4 : 2; }
 
 int adapter_run(Ctx& cx, const AdapterW& w, const AdapterCall& k) {
     TRY(begin_forward(cx));
@@ -782,12 +780,7 @@ int ctrl_adapter_param_spec(const ctrl_adapter_config* cfg, int i, char* name, i
     CTRL_CHECK(cfg && name && shape && ndim, "param_spec: null argument");
     SpecCollector sc; AdapterW w;
     TRY(build_adapter(sc, *cfg, &w));
-    CTRL_CHECK(i >= 0 && i < (int)sc.entries.size(), "param_spec: index out of range");
-    std::strncpy(name, sc.entries[i].name.c_str(), name_len - 1);
-    name[name_len - 1] = 0;
-    *ndim = (int)sc.entries[i].shape.size();
-    for (int k = 0; k < 6; ++k) shape[k] = k < *ndim ? sc.entries[i].shape[k] : 1;
-    return 0;
+    return spec_entry(sc, i, "param_spec", name, name_len, shape, ndim);
 }
 
 int ctrl_adapter_create(const ctrl_adapter_config* cfg, const ctrl_tensor_ref* tensors, int n_tensors, void* stream,

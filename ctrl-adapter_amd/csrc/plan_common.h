@@ -608,3 +608,5 @@ int run_layernorm(Ctx& cx, const Norm& n, const TV& x, half_t* y, int M, int dim
 constexpr int kFfnFusedMinM = 16384;
 int run_ffn(Ctx& cx, const Lin& ff1, const Lin& ff2, const half_t* xn, int dim, const TV& out, int M, const TV& res,
             const float* blend_mix = nullptr, const TV& blend_other = TV(), const Norm* ln = nullptr, half_t* ln_out = nullptr);
+
+#include "plan_shell.h"

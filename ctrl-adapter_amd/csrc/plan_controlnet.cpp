@@ -510,12 +510,7 @@ int ctrl_controlnet_param_spec(const ctrl_controlnet_config* cfg, int i, char* n
     CTRL_CHECK(cfg && name && shape && ndim, "param_spec: null argument");
     SpecCollector sc; ControlNetW w;
     TRY(build_controlnet(sc, *cfg, &w));
-    CTRL_CHECK(i >= 0 && i < (int)sc.entries.size(), "param_spec: index out of range");
-    std::strncpy(name, sc.entries[i].name.c_str(), name_len - 1);
-    name[name_len - 1] = 0;
-    *ndim = (int)sc.entries[i].shape.size();
-    for (int k = 0; k < 6; ++k) shape[k] = k < *ndim ? sc.entries[i].shape[k] : 1;
-    return 0;
+    return spec_entry(sc, i, "param_spec", name, name_len, shape, ndim);
 }
 
 int ctrl_controlnet_create(const ctrl_controlnet_config* cfg, const ctrl_tensor_ref* tensors, int n_tensors, void* stream,

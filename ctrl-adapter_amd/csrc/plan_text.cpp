@@ -6,30 +6,21 @@
 // other kernel computes rows or (prompt, head) pairs on their own, so a prompt's outputs are bit-identical whatever the batch it is in.
 // The ext plan (ctrl_text_encoder_create_ext: SDXL's OpenCLIP bigG text_encoder_2) adds exact gelu, hidden sizes up to 2048, the
 // fp32 text projection of the pooled row and the few-row GEMM of text_gemm.hip (gemm_form 1), equally batch-invariant.
-#include "plan_common.h"
-#include <algorithm>
+#include "plan_clip.h"
 #include <cmath>
 
 namespace {
 
-struct TextLayer {
-    Norm ln1, ln2;
-    Lin qkv, out, fc1, fc2;
-};
-
-struct TextEncoder : PlanBase {
+struct TextEncoder : StandalonePlan {
     ctrl_text_encoder_config cfg{};
     ctrl_text_encoder_ext ext{};     // zeros: quick_gelu, no projection, the pinned GEMM (what ctrl_text_encoder_create builds)
     float* proj = nullptr;           // text_projection.weight fp32 [projection_dim][hidden]
-    Packer* pk = nullptr;
     float* tok = nullptr;
     float* pos = nullptr;
-    std::vector<TextLayer> layers;
+    std::vector<ClipLayer> layers;
     Norm final_ln;
-    Arena ar;
     int* bad = nullptr;          // device flag word: an id outside the vocabulary was clamped
     ~TextEncoder() {
-        if (pk) { pk->release_all(); delete pk; }
         if (bad) (void)hipFree(bad);
     }
 };
@@ -48,20 +39,10 @@ int validate(const ctrl_text_encoder_config& c, int max_hidden) {
 
 int build_text(ParamSink& ps, TextEncoder& t) {
     const ctrl_text_encoder_config& c = t.cfg;
-    const int C = c.hidden_size, I = c.intermediate_size;
+    const int C = c.hidden_size;
     TRY(ps.raw_f32("text_model.embeddings.token_embedding.weight", {c.vocab_size, C}, &t.tok));
     TRY(ps.raw_f32("text_model.embeddings.position_embedding.weight", {c.max_position_embeddings, C}, &t.pos));
-    t.layers.resize(c.num_hidden_layers);
-    for (int i = 0; i < c.num_hidden_layers; ++i) {
-        const std::string pre = "text_model.encoder.layers." + std::to_string(i) + ".";
-        TextLayer& l = t.layers[i];
-        TRY(ps.norm(pre + "layer_norm1", C, &l.ln1));
-        TRY(ps.linear_cat({pre + "self_attn.q_proj", pre + "self_attn.k_proj", pre + "self_attn.v_proj"}, {C, C, C}, C, true, &l.qkv));
-        TRY(ps.linear(pre + "self_attn.out_proj", C, C, true, false, &l.out));
-        TRY(ps.norm(pre + "layer_norm2", C, &l.ln2));
-        TRY(ps.linear(pre + "mlp.fc1", I, C, true, false, &l.fc1));
-        TRY(ps.linear(pre + "mlp.fc2", C, I, true, false, &l.fc2));
-    }
+    TRY(build_clip_layers(ps, "text_model.encoder.layers.", c.num_hidden_layers, C, c.intermediate_size, &t.layers));
     TRY(ps.norm("text_model.final_layer_norm", C, &t.final_ln));
     if (t.ext.projection_dim > 0) TRY(ps.raw_f32("text_projection.weight", {t.ext.projection_dim, C}, &t.proj));
     return 0;
@@ -73,41 +54,6 @@ int validate_ext(const ctrl_text_encoder_ext& e) {
     CTRL_CHECK(e.gemm_form == 0 || e.gemm_form == 1, "text encoder: gemm_form must be 0 (pinned) or 1 (few-row GEMM)");
     CTRL_CHECK(e.reserved == 0, "text encoder: ctrl_text_encoder_ext.reserved must be 0");
     return 0;
-}
-
-// row-major linear on the pinned GEMM: y[M][N] (dtype of y) = act(x[M][K] W^T + b) (+ fp32 residual)
-int linear(const Lin& l, const half_t* x, void* y, int y_dt, int M, const float* res, int act, hipStream_t s) {
-    IGemmArgs g = {};
-    g.A = x; g.lda = l.K; g.mode = IG_ROWS; g.Cin = l.K; g.taps = 1;
-    g.W = l.w; g.M = M; g.Nout = l.N; g.Ktot = l.K; g.bias = l.b; g.scale = 1.f; g.act = act;
-    g.res = res; g.ldres = l.N; g.res_f32 = res ? 1 : 0;
-    g.nseg = 1;
-    g.seg[0] = IGemmSeg{y, l.N, 0, l.N, SEG_ROW, y_dt, 1, 0, nullptr};
-    return op_igemm_pinned(g, s);
-}
-
-size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// scratch a linear of the plan's form needs besides its output: the split-K partials (form 1) or the fp32 pre-activation of an
-// exact-gelu fc1 on the pinned form (form 0: the shared implicit-GEMM epilogue has no erf; the fp32 pass applies it in the same order,
-// bias -> act -> residual)
-struct LinScratch { float* p = nullptr; size_t bytes = 0; };
-
-int run_linear(const TextEncoder& t, const Lin& l, const half_t* x, void* y, int y_dt, int M, const float* res, int act, const LinScratch& ws,
-               hipStream_t s) {
-    if (t.ext.gemm_form == 1) return op_text_gemm(x, l.w, l.b, M, l.N, l.K, act, res, y, y_dt, ws.p, ws.bytes, s);
-    if (act != 3) return linear(l, x, y, y_dt, M, res, act, s);
-    TRY(linear(l, x, ws.p, DT_F32, M, nullptr, 0, s));
-    return op_text_gemm_finish(ws.p, 1, M, l.N, nullptr, 3, res, l.N, y, y_dt, l.N, s);
-}
-
-size_t lin_scratch_bytes(const TextEncoder& t, int M) {
-    const ctrl_text_encoder_config& c = t.cfg;
-    const size_t C = c.hidden_size, I = c.intermediate_size;
-    if (t.ext.gemm_form == 1)
-        return std::max(std::max(text_gemm_ws_bytes(M, 3 * C, C), text_gemm_ws_bytes(M, C, C)),
-                        std::max(text_gemm_ws_bytes(M, I, C), text_gemm_ws_bytes(M, C, I)));
-    return t.ext.hidden_act == 1 ? (size_t)M * I * 4 : 0;
 }
 
 // hidden_index -1: every state into hidden [layers + 1][N][L][C]; k >= 0: state k alone into hidden [N][L][C], and with no
@@ -123,106 +69,64 @@ int forward(TextEncoder& t, const int64_t* ids, int N, int L, void* last, void* 
     CTRL_CHECK(!embeds || t.proj, "text encoder: text_embeds needs a plan with a text projection (projection_dim > 0)");
     const int C = c.hidden_size, I = c.intermediate_size, M = N * L;
     const float eps = c.layer_norm_eps;
-    const bool tail = last || pooled || embeds;
-    const int layers = (!tail && hidden_index >= 0) ? hidden_index : c.num_hidden_layers;
+    const int layers = clip_layers_to_run(last || pooled || embeds, hidden_index, c.num_hidden_layers);
     // workspace: two fp32 stream buffers, the fp16 LayerNorm output, Q | K | V, the attention output, the MLP hidden activation
     // (+ the linears' scratch and the fp32 pooled rows of the projection)
     const size_t b_x = al256((size_t)M * C * 4), b_h = al256((size_t)M * C * 2), b_qkv = al256((size_t)M * 3 * C * 2),
-                 b_ff = al256((size_t)M * I * 2), b_lin = al256(lin_scratch_bytes(t, M)), b_p32 = t.proj ? al256((size_t)N * C * 4) : 0;
-    const size_t need = 2 * b_x + 2 * b_h + b_qkv + b_ff + b_lin + b_p32;
+                 b_ff = al256((size_t)M * I * 2), b_lin = al256(lin_scratch_bytes(t.ext.gemm_form, t.ext.hidden_act, M, C, I)),
+                 b_p32 = t.proj ? al256((size_t)N * C * 4) : 0;
     bool capturing = false;
     TRY(t.enter(s, &capturing));
-    CTRL_CHECK(!capturing || need <= t.ar.cap, "text encoder: the first forward of a larger batch allocates its workspace and cannot run "
-                                               "under stream capture -- run it eagerly once, then capture");
-    TRY(t.ar.ensure(need));
+    TRY(t.reserve(2 * b_x + 2 * b_h + b_qkv + b_ff + b_lin + b_p32, capturing, "text encoder", "batch"));
     char* p = t.ar.base;
-    float* xa = (float*)p; p += b_x;
-    float* xb = (float*)p; p += b_x;
-    half_t* h16 = (half_t*)p; p += b_h;
-    half_t* ao = (half_t*)p; p += b_h;
-    half_t* qkv = (half_t*)p; p += b_qkv;
-    half_t* ff = (half_t*)p; p += b_ff;
-    LinScratch lws;
-    lws.p = b_lin ? (float*)p : nullptr; lws.bytes = b_lin; p += b_lin;
+    ClipBufs b;
+    b.xa = (float*)p; p += b_x;
+    b.xb = (float*)p; p += b_x;
+    b.h16 = (half_t*)p; p += b_h;
+    b.ao = (half_t*)p; p += b_h;
+    b.qkv = (half_t*)p; p += b_qkv;
+    b.ff = (half_t*)p; p += b_ff;
+    b.lws.p = b_lin ? (float*)p : nullptr; b.lws.bytes = b_lin; p += b_lin;
     float* p32 = b_p32 ? (float*)p : nullptr;
-    const size_t esz = odt == DT_F32 ? 4 : 2;
-    auto snap = [&](int k, const float* x) -> int {     // hidden_states[k] = the stream after k layers
-        if (!hidden || (hidden_index >= 0 && k != hidden_index)) return 0;
-        const size_t slot = hidden_index >= 0 ? 0 : (size_t)k;
-        return op_text_store(x, (char*)hidden + slot * M * C * esz, odt, (size_t)M * C, s);
-    };
-    const int fc1_act = t.ext.hidden_act == 1 ? 3 : 2;
-    TRY(op_text_embed(ids, t.tok, t.pos, c.vocab_size, N, L, C, xa, t.layers[0].ln1.g, t.layers[0].ln1.b, eps, h16, t.bad, s));
-    TRY(snap(0, xa));
+    const ClipSnapshot snap{hidden, hidden_index, odt, (size_t)M * C};
+    TRY(op_text_embed(ids, t.tok, t.pos, c.vocab_size, N, L, C, b.xa, t.layers[0].ln1.g, t.layers[0].ln1.b, eps, b.h16, t.bad, s));
+    TRY(snap(0, b.xa, s));
     const float scale = 1.0f / std::sqrt(64.0f);
-    for (int i = 0; i < layers; ++i) {
-        const TextLayer& l = t.layers[i];
-        TRY(run_linear(t, l.qkv, h16, qkv, DT_F16, M, nullptr, 0, lws, s));
-        TRY(op_text_attn(qkv, 3L * C, ao, C, N, L, c.num_attention_heads, scale, s));
-        TRY(run_linear(t, l.out, ao, xb, DT_F32, M, xa, 0, lws, s));
-        TRY(op_layernorm(xb, DT_F32, C, l.ln2.g, l.ln2.b, h16, C, M, C, eps, s));
-        TRY(run_linear(t, l.fc1, h16, ff, DT_F16, M, nullptr, fc1_act, lws, s));
-        TRY(run_linear(t, l.fc2, ff, xa, DT_F32, M, xb, 0, lws, s));
-        TRY(snap(i + 1, xa));
-        if (i + 1 < layers)
-            TRY(op_layernorm(xa, DT_F32, C, t.layers[i + 1].ln1.g, t.layers[i + 1].ln1.b, h16, C, M, C, eps, s));
-    }
+    TRY(run_clip_layers(t.layers, layers, t.ext.gemm_form, t.ext.hidden_act, M, C, eps, b, snap, s,
+                        [&] { return op_text_attn(b.qkv, 3L * C, b.ao, C, N, L, c.num_attention_heads, scale, s); }));
     if (last || pooled || embeds)
-        TRY(op_text_final_ext(xa, DT_F32, M, C, t.final_ln.g, t.final_ln.b, eps, last, odt, ids, L, c.eos_token_id, pooled,
+        TRY(op_text_final_ext(b.xa, DT_F32, M, C, t.final_ln.g, t.final_ln.b, eps, last, odt, ids, L, c.eos_token_id, pooled,
                               embeds ? p32 : nullptr, s));
     if (embeds) TRY(op_text_proj(p32, t.proj, N, C, t.ext.projection_dim, embeds, odt, s));
     return t.leave(s, capturing);
 }
 
-int create(const ctrl_text_encoder_config* cfg, const ctrl_text_encoder_ext* ext, const ctrl_tensor_ref* tensors, int n_tensors, void* stream,
-           ctrl_text_encoder** out) {
-    TextEncoder* t = new TextEncoder();
-    t->cfg = *cfg;
-    if (ext) t->ext = *ext;
-    int rc = t->init_base(n_tensors ? tensors[0].data : nullptr);
-    DeviceGuard dg(t->device);
-    if (!rc) {
-        t->pk = new Packer(tensors, n_tensors, (hipStream_t)stream);
-        rc = build_text(*t->pk, *t);
-        if (!rc) rc = t->pk->finish();
-    }
-    if (!rc && hipMalloc((void**)&t->bad, sizeof(int)) != hipSuccess) { ctrl_set_error("text_encoder_create: hipMalloc failed"); rc = 1; }
-    if (!rc && hipMemset(t->bad, 0, sizeof(int)) != hipSuccess) { ctrl_set_error("text_encoder_create: hipMemset failed"); rc = 1; }
-    if (rc) { delete t; return rc; }
-    *out = (ctrl_text_encoder*)t;
+// the device flag word of the ids, after the build
+int alloc_bad(TextEncoder& t, hipStream_t) {
+    if (hipMalloc((void**)&t.bad, sizeof(int)) != hipSuccess) { ctrl_set_error("text_encoder_create: hipMalloc failed"); return 1; }
+    if (hipMemset(t.bad, 0, sizeof(int)) != hipSuccess) { ctrl_set_error("text_encoder_create: hipMemset failed"); return 1; }
     return 0;
 }
 
 }  // namespace
 
-#define S(stream) ((hipStream_t)(stream))
-
 extern "C" {
 
 int ctrl_text_encoder_create(const ctrl_text_encoder_config* cfg, const ctrl_tensor_ref* tensors, int n_tensors, void* stream,
                              ctrl_text_encoder** out) {
-    CTRL_CHECK(cfg && out && (tensors || n_tensors == 0), "text_encoder_create: null argument");
-    *out = nullptr;
-    TRY(validate(*cfg, 1024));
-    return create(cfg, nullptr, tensors, n_tensors, stream, out);
+    return plan_create<TextEncoder>("text_encoder_create", cfg, tensors, n_tensors, stream, (void**)out,
+                                    [](const ctrl_text_encoder_config& c) { return validate(c, 1024); }, build_text, alloc_bad);
 }
 
 int ctrl_text_encoder_create_ext(const ctrl_text_encoder_config* cfg, const ctrl_text_encoder_ext* ext, const ctrl_tensor_ref* tensors,
                                  int n_tensors, void* stream, ctrl_text_encoder** out) {
-    CTRL_CHECK(cfg && ext && out && (tensors || n_tensors == 0), "text_encoder_create_ext: null argument");
-    *out = nullptr;
-    TRY(validate(*cfg, 2048));
-    TRY(validate_ext(*ext));
-    return create(cfg, ext, tensors, n_tensors, stream, out);
+    CTRL_CHECK(ext, "text_encoder_create_ext: null argument");
+    return plan_create<TextEncoder>("text_encoder_create_ext", cfg, tensors, n_tensors, stream, (void**)out,
+                                    [&](const ctrl_text_encoder_config& c) { TRY(validate(c, 2048)); return validate_ext(*ext); },
+                                    [&](ParamSink& ps, TextEncoder& t) { t.ext = *ext; return build_text(ps, t); }, alloc_bad);
 }
 
-void ctrl_text_encoder_destroy(ctrl_text_encoder* h) {
-    if (!h) return;
-    TextEncoder* t = (TextEncoder*)h;
-    DeviceGuard dg(t->device);
-    (void)hipDeviceSynchronize();        // queued launches and captured graphs may still address the workspace
-    delete t;
-}
+void ctrl_text_encoder_destroy(ctrl_text_encoder* h) { plan_destroy<TextEncoder>(h); }
 
 int ctrl_text_encoder_forward(ctrl_text_encoder* h, const int64_t* input_ids, int N, int L, void* last_hidden, void* pooled,
                               void* hidden_states, int out_dtype, void* stream) {

@@ -7,46 +7,25 @@
 //   the last stream | tail kernel (conv_norm_out + SiLU + conv_out + the output epilogue in one pass, fp32, vae.hip).
 // As in the encoder plan (plan_vae.cpp) the residual stream is fp32 from conv_in on, every implicit-GEMM convolution reads a split
 // [hi | lo] fp16 operand, the attention's Q / K / V / P are fp16, and images run one after the other through the same launches (an image's
-// pixels are bit-identical whatever the batch).  conv_out's input never leaves fp32.  The first forward of a larger latent size allocates
+// pixels are bit-identical whatever the batch).  conv_out's input never leaves fp32.  The first forward at a larger latent size allocates
 // the workspace; every later forward allocates nothing and is capturable.
-#include "plan_common.h"
-#include <algorithm>
-#include <cstring>
+#include "plan_vae_common.h"
 
 namespace {
 
-struct DecLevel {
-    std::vector<ResnetW> res;
-    bool up = false;
-    ConvW up_conv;
-};
-
-struct VaeDecoder : PlanBase {
+struct VaeDecoder : StandalonePlan {
     ctrl_vae_decoder_config cfg{};
-    Packer* pk = nullptr;
     float* wpq = nullptr;         // post_quant_conv.weight fp32 [lat][lat]
     float* bpq = nullptr;
     ConvD conv_in;                // fp32 [9][lat][C_top]
-    ResnetW mid0, mid1;
-    Norm attn_gn, norm_out;
-    Lin qkv, attn_out;
-    std::vector<DecLevel> levels;
+    VaeMid mid;
+    Norm norm_out;
+    std::vector<VaeLevel> levels;
     ConvD conv_out;               // fp32 [9][C0][out_channels]
-    Arena ar;
-    ~VaeDecoder() {
-        if (pk) { pk->release_all(); delete pk; }
-    }
 };
 
 int validate(const ctrl_vae_decoder_config& c) {
-    CTRL_CHECK(c.num_levels >= 1 && c.num_levels <= 4, "vae decoder: 1 to 4 levels (block_out_channels)");
-    for (int i = 0; i < c.num_levels; ++i)
-        CTRL_CHECK(c.block_out_channels[i] >= 32 && c.block_out_channels[i] <= 2048 && c.block_out_channels[i] % 32 == 0,
-                   "vae decoder: block_out_channels must be multiples of 32 up to 2048");
-    CTRL_CHECK(c.layers_per_block >= 1 && c.layers_per_block <= 8, "vae decoder: layers_per_block must be 1 .. 8");
-    CTRL_CHECK(c.latent_channels >= 1 && c.latent_channels <= 8, "vae decoder: latent_channels must be 1 .. 8");
-    CTRL_CHECK(c.norm_num_groups == 32, "vae decoder: norm_num_groups must be 32");
-    CTRL_CHECK(c.norm_eps > 0.f, "vae decoder: norm_eps must be positive");
+    TRY(validate_vae(c, "vae decoder"));
     CTRL_CHECK(c.out_channels >= 1 && c.out_channels <= 4, "vae decoder: out_channels must be 1 .. 4");
     return 0;
 }
@@ -57,29 +36,22 @@ int build_dec(ParamSink& ps, VaeDecoder& t) {
     TRY(ps.raw_f32("post_quant_conv.weight", {lat, lat, 1, 1}, &t.wpq));
     TRY(ps.raw_f32("post_quant_conv.bias", {lat}, &t.bpq));
     TRY(ps.conv_direct("decoder.conv_in", Ct, lat, &t.conv_in));
-    TRY(build_resnet(ps, "decoder.mid_block.resnets.0", Ct, Ct, false, &t.mid0, true));
-    const std::string ap = "decoder.mid_block.attentions.0.";
-    TRY(ps.norm(ap + "group_norm", Ct, &t.attn_gn));
-    TRY(ps.linear_cat({ap + "to_q", ap + "to_k", ap + "to_v"}, {Ct, Ct, Ct}, Ct, true, &t.qkv));
-    TRY(ps.linear(ap + "to_out.0", Ct, Ct, true, false, &t.attn_out));
-    TRY(build_resnet(ps, "decoder.mid_block.resnets.1", Ct, Ct, false, &t.mid1, true));
+    TRY(build_vae_mid(ps, "decoder.", Ct, &t.mid));
     t.levels.resize(nl);
     int cin = Ct;
-    for (int i = 0; i < nl; ++i) {
-        const int cout = c.block_out_channels[nl - 1 - i];
-        DecLevel& lv = t.levels[i];
-        lv.res.resize(c.layers_per_block + 1);
-        const std::string pre = "decoder.up_blocks." + std::to_string(i) + ".";
-        for (int j = 0; j <= c.layers_per_block; ++j) {
-            TRY(build_resnet(ps, pre + "resnets." + std::to_string(j), cin, cout, false, &lv.res[j], true));
-            cin = cout;
-        }
-        lv.up = i + 1 < nl;
-        if (lv.up) TRY(ps.conv(pre + "upsamplers.0.conv", cout, cout, 3, false, &lv.up_conv, true));
-    }
+    for (int i = 0; i < nl; ++i)
+        TRY(build_vae_level(ps, "decoder.up_blocks." + std::to_string(i) + ".", c.layers_per_block + 1, &cin, c.block_out_channels[nl - 1 - i],
+                            i + 1 < nl, "upsamplers.0.conv", &t.levels[i]));
     TRY(ps.norm("decoder.conv_norm_out", cin, &t.norm_out));
     TRY(ps.conv_direct("decoder.conv_out", c.out_channels, cin, &t.conv_out));
     return 0;
+}
+
+int collect(const ctrl_vae_decoder_config& c, SpecCollector& sc) {
+    TRY(validate(c));
+    VaeDecoder t;
+    t.cfg = c;
+    return build_dec(sc, t);
 }
 
 struct DecFwd {
@@ -88,8 +60,6 @@ struct DecFwd {
     float scale; int kind;
     void* out; int odt;
 };
-
-size_t dt_size(int dt) { return dt == DT_F32 ? 4 : 2; }
 
 // one image through the decoder: latents of image n -> its pixels
 int run_image(Ctx& cx, const VaeDecoder& t, const DecFwd& a, int n) {
@@ -105,47 +75,24 @@ int run_image(Ctx& cx, const VaeDecoder& t, const DecFwd& a, int n) {
         int cin = Ct;
         size_t hw = (size_t)a.h * a.w;
         for (int i = 0; i < nl; ++i) {
-            const DecLevel& lv = t.levels[i];
+            const VaeLevel& lv = t.levels[i];
             const int cout = lv.res[0].Cout;
             max32 = std::max(max32, hw * std::max(cin, cout));
             if (lv.res[0].has_shortcut) max16 = std::max(max16, hw * cin);
-            if (lv.up) { max16 = std::max(max16, hw * cout); hw *= 4; max32 = std::max(max32, hw * cout); }
+            if (lv.resample) { max16 = std::max(max16, hw * cout); hw *= 4; max32 = std::max(max32, hw * cout); }
             cin = cout;
         }
     }
-    float* s32[2] = {cx.f(max32), cx.f(max32)};
-    half_t* s16[2] = {max16 ? cx.h(2 * max16) : nullptr, max16 ? cx.h(2 * max16) : nullptr};
-    int cur = 0;
-    auto next = [&](bool need16, int C) {
-        cur ^= 1;
-        TV v; v.p = s32[cur]; v.dt = DT_F32; v.m16 = need16 ? s16[cur] : nullptr; v.lo_off = need16 ? C : 0;
-        return v;
-    };
+    VaeStreams streams(cx, max32, max16);
     int h = a.h, w = a.w;
     const char* z = (const char*)a.z + (size_t)n * a.img_stride * dt_size(a.zdt);
-    RUN(cx, op_vae_dec_head(z, a.zdt, a.scale, t.wpq, t.bpq, t.conv_in.w, t.conv_in.b, s32[0], lat, h, w, a.ch_stride, Ct, cx.s));
-    TV x; x.p = s32[0]; x.dt = DT_F32;
-    { TV y = next(false, Ct); TRY(run_resnet(cx, t.mid0, x, y, 1, h, w, 1, nullptr, 0, eps)); x = y; }
-    { TV y = next(false, Ct); TRY(run_vae_mid_attention(cx, t.attn_gn, t.qkv, t.attn_out, Ct, eps, x, y, h * w)); x = y; }
-    { TV y = next(t.levels[0].res[0].has_shortcut, Ct); TRY(run_resnet(cx, t.mid1, x, y, 1, h, w, 1, nullptr, 0, eps)); x = y; }
+    RUN(cx, op_vae_dec_head(z, a.zdt, a.scale, t.wpq, t.bpq, t.conv_in.w, t.conv_in.b, streams.s32[0], lat, h, w, a.ch_stride, Ct, cx.s));
+    TV x = streams.first();
+    TRY(run_vae_mid(cx, streams, t.mid, &x, t.levels[0].res[0].has_shortcut, h, w, eps));
+    ConvOpts up; up.up = 2;                    // nearest x2 in the gather
     for (int i = 0; i < nl; ++i) {
-        const DecLevel& lv = t.levels[i];
-        for (int j = 0; j < (int)lv.res.size(); ++j) {
-            bool need16 = false;
-            if (j + 1 < (int)lv.res.size()) need16 = lv.res[j + 1].has_shortcut;
-            else if (lv.up) need16 = true;
-            TV y = next(need16, lv.res[j].Cout);
-            TRY(run_resnet(cx, lv.res[j], x, y, 1, h, w, 1, nullptr, 0, eps));
-            x = y;
-        }
-        if (lv.up) {
-            const int C = lv.res.back().Cout;
-            TV y = next(t.levels[i + 1].res[0].has_shortcut, C);
-            ConvOpts o; o.up = 2;
-            TRY(run_conv(cx, lv.up_conv, x.m16, y, 1, h, w, o));        // nearest x2 in the gather, on the split mirror
-            h *= 2; w *= 2;
-            x = y;
-        }
+        TRY(run_vae_level(cx, streams, t.levels[i], up, i + 1 < nl && t.levels[i + 1].res[0].has_shortcut, &x, h, w, eps));
+        if (t.levels[i].resample) { h *= 2; w *= 2; }
     }
     const int C0 = t.norm_out.C, oc = c.out_channels;
     float* st = cx.stats(op_gn_stats_floats(1, h * w, C0, 32));
@@ -185,81 +132,32 @@ int forward(VaeDecoder& t, const DecFwd& a, int N, hipStream_t s) {
     }
     CTRL_CHECK(a.kind == CTRL_VAE_DEC_SAMPLE || a.kind == CTRL_VAE_DEC_UNIT || a.kind == CTRL_VAE_DEC_U8, "vae decoder: kind must be 0, 1 or 2");
     CTRL_CHECK(a.odt == DT_F32 || a.odt == DT_F16 || a.odt == DT_BF16, "vae decoder: out_dtype must be fp32, fp16 or bf16");
-    bool capturing = false;
-    TRY(t.enter(s, &capturing));
-    t.ar.off = 0; t.ar.peak = 0;
-    Ctx dry{&t.ar, s, true};
-    dry.f32stream = true;
-    TRY(run_image(dry, t, a, 0));
-    const size_t need = workspace_bytes(dry);
-    CTRL_CHECK(!capturing || need <= t.ar.cap, "vae decoder: the first forward of a larger image allocates its workspace and cannot run "
-                                               "under stream capture -- run it eagerly once, then capture");
-    TRY(t.ar.ensure(need));
-    Ctx cx{&t.ar, s, false};
-    cx.f32stream = true;
-    cx.capturing = capturing;
-    cx.stats_total = dry.stats_total;
-    for (int n = 0; n < N; ++n) {
-        t.ar.off = 0;
-        TRY(run_image(cx, t, a, n));
-    }
-    return t.leave(s, capturing);
+    return run_per_image(t, N, s, "vae decoder", [&](Ctx& cx, int n) { return run_image(cx, t, a, n); });
 }
 
 }  // namespace
 
-#define S(stream) ((hipStream_t)(stream))
-
 extern "C" {
 
 int ctrl_vae_decoder_param_count(const ctrl_vae_decoder_config* cfg) {
-    if (!cfg || validate(*cfg)) return -1;
-    SpecCollector sc; VaeDecoder t;
-    t.cfg = *cfg;
-    if (build_dec(sc, t)) return -1;
-    return (int)sc.entries.size();
+    SpecCollector sc;
+    return (cfg && !collect(*cfg, sc)) ? (int)sc.entries.size() : -1;
 }
 
 int ctrl_vae_decoder_param_spec(const ctrl_vae_decoder_config* cfg, int i, char* name, int name_len, int64_t shape[6], int* ndim) {
     CTRL_CHECK(cfg && name && shape && ndim && name_len >= 1, "vae_decoder_param_spec: null argument");
-    TRY(validate(*cfg));
-    SpecCollector sc; VaeDecoder t;
-    t.cfg = *cfg;
-    TRY(build_dec(sc, t));
-    CTRL_CHECK(i >= 0 && i < (int)sc.entries.size(), "vae_decoder_param_spec: index out of range");
-    std::strncpy(name, sc.entries[i].name.c_str(), name_len - 1);
-    name[name_len - 1] = 0;
-    *ndim = (int)sc.entries[i].shape.size();
-    for (int k = 0; k < 6; ++k) shape[k] = k < *ndim ? sc.entries[i].shape[k] : 1;
-    return 0;
+    SpecCollector sc;
+    TRY(collect(*cfg, sc));
+    return spec_entry(sc, i, "vae_decoder_param_spec", name, name_len, shape, ndim);
 }
 
 int ctrl_vae_decoder_create(const ctrl_vae_decoder_config* cfg, const ctrl_tensor_ref* tensors, int n_tensors, void* stream,
                             ctrl_vae_decoder** out) {
-    CTRL_CHECK(cfg && out && (tensors || n_tensors == 0), "vae_decoder_create: null argument");
-    *out = nullptr;
-    TRY(validate(*cfg));
-    VaeDecoder* t = new VaeDecoder();
-    t->cfg = *cfg;
-    int rc = t->init_base(n_tensors ? tensors[0].data : nullptr);
-    DeviceGuard dg(t->device);
-    if (!rc) {
-        t->pk = new Packer(tensors, n_tensors, (hipStream_t)stream);
-        rc = build_dec(*t->pk, *t);
-        if (!rc) rc = t->pk->finish();
-    }
-    if (rc) { delete t; return rc; }
-    *out = (ctrl_vae_decoder*)t;
-    return 0;
+    return plan_create<VaeDecoder>("vae_decoder_create", cfg, tensors, n_tensors, stream, (void**)out, validate, build_dec,
+                                   [](VaeDecoder&, hipStream_t) { return 0; });
 }
 
-void ctrl_vae_decoder_destroy(ctrl_vae_decoder* h) {
-    if (!h) return;
-    VaeDecoder* t = (VaeDecoder*)h;
-    DeviceGuard dg(t->device);
-    (void)hipDeviceSynchronize();        // queued launches and captured graphs may still address the workspace
-    delete t;
-}
+void ctrl_vae_decoder_destroy(ctrl_vae_decoder* h) { plan_destroy<VaeDecoder>(h); }
 
 int ctrl_vae_decoder_forward_strided(ctrl_vae_decoder* h, const void* latents, int latent_dtype, int N, int lat_h, int lat_w,
                                      int64_t image_stride, int64_t channel_stride, float scale, int kind, void* out, int out_dtype,

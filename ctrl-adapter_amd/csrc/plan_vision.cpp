@@ -9,33 +9,21 @@
 // (gemm_form 0: the pinned 64 x 64 x 64 implicit GEMM; 1: the few-row split-K GEMM of text_gemm.hip; the patch GEMM is always the
 // pinned one) and every other kernel computes rows, tiles of one image or (image, head, query tile) on its own: an image's outputs are
 // bit-identical whatever the batch it is in.
-#include "plan_common.h"
-#include <algorithm>
+#include "plan_clip.h"
 #include <cmath>
-#include <cstring>
 
 namespace {
 
-struct VisionLayer {
-    Norm ln1, ln2;
-    Lin qkv, out, fc1, fc2;
-};
-
-struct VisionEncoder : PlanBase {
+struct VisionEncoder : StandalonePlan {
     ctrl_vision_encoder_config cfg{};
     int P = 0, L = 0, K = 0, Kpad = 0, Lkpad = 0, D = 0;
-    Packer* pk = nullptr;
     float* cls = nullptr;          // class_embedding fp32 [C]
     float* pos = nullptr;          // position_embedding fp32 [L][C]
     float* patch32 = nullptr;      // patch_embedding.weight fp32 [C][3][p][p] (packed to patch_w)
     half_t* patch_w = nullptr;     // fp16 [C][Kpad]
     float* proj = nullptr;         // visual_projection.weight fp32 [P][C]
     Norm pre_ln, post_ln;
-    std::vector<VisionLayer> layers;
-    Arena ar;
-    ~VisionEncoder() {
-        if (pk) { pk->release_all(); delete pk; }
-    }
+    std::vector<ClipLayer> layers;
 };
 
 int validate(const ctrl_vision_encoder_config& c) {
@@ -57,71 +45,37 @@ int validate(const ctrl_vision_encoder_config& c) {
     return 0;
 }
 
-void derive(VisionEncoder& t) {
-    const ctrl_vision_encoder_config& c = t.cfg;
-    const int G = c.image_size / c.patch_size;
-    t.P = G * G;
-    t.L = t.P + 1;
-    t.K = 3 * c.patch_size * c.patch_size;
-    t.Kpad = (t.K + 63) / 64 * 64;
-    t.Lkpad = (t.L + 63) / 64 * 64;
-    t.D = c.hidden_size / c.num_attention_heads;
-}
-
+// the token / patch geometry of the config, then the parameters
 int build_vision(ParamSink& ps, VisionEncoder& t) {
     const ctrl_vision_encoder_config& c = t.cfg;
-    const int C = c.hidden_size, I = c.intermediate_size, p = c.patch_size;
+    const int C = c.hidden_size, p = c.patch_size, G = c.image_size / p;
+    t.P = G * G;
+    t.L = t.P + 1;
+    t.K = 3 * p * p;
+    t.Kpad = (t.K + 63) / 64 * 64;
+    t.Lkpad = (t.L + 63) / 64 * 64;
+    t.D = C / c.num_attention_heads;
     TRY(ps.raw_f32("vision_model.embeddings.class_embedding", {C}, &t.cls));
     TRY(ps.raw_f32("vision_model.embeddings.patch_embedding.weight", {C, 3, p, p}, &t.patch32));
     TRY(ps.raw_f32("vision_model.embeddings.position_embedding.weight", {t.L, C}, &t.pos));
     TRY(ps.norm("vision_model.pre_layrnorm", C, &t.pre_ln));
-    t.layers.resize(c.num_hidden_layers);
-    for (int i = 0; i < c.num_hidden_layers; ++i) {
-        const std::string pre = "vision_model.encoder.layers." + std::to_string(i) + ".";
-        VisionLayer& l = t.layers[i];
-        TRY(ps.norm(pre + "layer_norm1", C, &l.ln1));
-        TRY(ps.linear_cat({pre + "self_attn.q_proj", pre + "self_attn.k_proj", pre + "self_attn.v_proj"}, {C, C, C}, C, true, &l.qkv));
-        TRY(ps.linear(pre + "self_attn.out_proj", C, C, true, false, &l.out));
-        TRY(ps.norm(pre + "layer_norm2", C, &l.ln2));
-        TRY(ps.linear(pre + "mlp.fc1", I, C, true, false, &l.fc1));
-        TRY(ps.linear(pre + "mlp.fc2", C, I, true, false, &l.fc2));
-    }
+    TRY(build_clip_layers(ps, "vision_model.encoder.layers.", c.num_hidden_layers, C, c.intermediate_size, &t.layers));
     TRY(ps.norm("vision_model.post_layernorm", C, &t.post_ln));
     TRY(ps.raw_f32("visual_projection.weight", {c.projection_dim, C}, &t.proj));
     return 0;
 }
 
-// row-major linear on the pinned GEMM: y[M][N] (dtype of y) = act(x[M][K] W^T + b) (+ fp32 residual)
-int pinned(const half_t* x, const half_t* W, const float* b, int N, int K, void* y, int y_dt, int M, const float* res, int act, hipStream_t s) {
-    IGemmArgs g = {};
-    g.A = x; g.lda = K; g.mode = IG_ROWS; g.Cin = K; g.taps = 1;
-    g.W = W; g.M = M; g.Nout = N; g.Ktot = K; g.bias = b; g.scale = 1.f; g.act = act;
-    g.res = res; g.ldres = N; g.res_f32 = res ? 1 : 0;
-    g.nseg = 1;
-    g.seg[0] = IGemmSeg{y, N, 0, N, SEG_ROW, y_dt, 1, 0, nullptr};
-    return op_igemm_pinned(g, s);
+// patch_embedding.weight as the patch GEMM's fp16 [C][Kpad] operand
+int pack_patch_w(VisionEncoder& t, hipStream_t s) {
+    TRY(t.pk->dalloc((size_t)t.cfg.hidden_size * t.Kpad * sizeof(half_t), (void**)&t.patch_w));
+    return op_vision_pack_patch(t.patch32, t.cfg.hidden_size, t.K, t.Kpad, t.patch_w, s);
 }
 
-size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-struct LinScratch { float* p = nullptr; size_t bytes = 0; };
-
-// the linear of the plan's form (act 2 quick_gelu, 3 exact gelu); exact gelu on the pinned form is a separate fp32 pass in the same
-// order as the fused epilogues (bias -> act -> residual), as in plan_text.cpp
-int run_linear(const VisionEncoder& t, const Lin& l, const half_t* x, void* y, int y_dt, int M, const float* res, int act, const LinScratch& ws,
-               hipStream_t s) {
-    if (t.cfg.gemm_form == 1) return op_text_gemm(x, l.w, l.b, M, l.N, l.K, act, res, y, y_dt, ws.p, ws.bytes, s);
-    if (act != 3) return pinned(x, l.w, l.b, l.N, l.K, y, y_dt, M, res, act, s);
-    TRY(pinned(x, l.w, l.b, l.N, l.K, ws.p, DT_F32, M, nullptr, 0, s));
-    return op_text_gemm_finish(ws.p, 1, M, l.N, nullptr, 3, res, l.N, y, y_dt, l.N, s);
-}
-
-size_t lin_scratch_bytes(const VisionEncoder& t, int M) {
-    const size_t C = t.cfg.hidden_size, I = t.cfg.intermediate_size;
-    if (t.cfg.gemm_form == 1)
-        return std::max(std::max(text_gemm_ws_bytes(M, 3 * C, C), text_gemm_ws_bytes(M, C, C)),
-                        std::max(text_gemm_ws_bytes(M, I, C), text_gemm_ws_bytes(M, C, I)));
-    return t.cfg.hidden_act == 1 ? (size_t)M * I * 4 : 0;
+int collect(const ctrl_vision_encoder_config& c, SpecCollector& sc) {
+    TRY(validate(c));
+    VisionEncoder t;
+    t.cfg = c;
+    return build_vision(sc, t);
 }
 
 int forward(VisionEncoder& t, const void* px, int pdt, int N, const float* mean_std, void* last, void* pooled, void* embeds, void* hidden,
@@ -135,60 +89,43 @@ int forward(VisionEncoder& t, const void* px, int pdt, int N, const float* mean_
     CTRL_CHECK(hidden_index >= -1 && hidden_index <= c.num_hidden_layers, "vision encoder: hidden_index must be -1 .. num_hidden_layers");
     const int C = c.hidden_size, I = c.intermediate_size, L = t.L, M = N * L, Mp = N * t.P;
     const float eps = c.layer_norm_eps;
-    const bool tail = last || pooled || embeds;
-    const int layers = (!tail && hidden_index >= 0) ? hidden_index : c.num_hidden_layers;
+    const int layers = clip_layers_to_run(last || pooled || embeds, hidden_index, c.num_hidden_layers);
     // workspace: im2col rows + the patch GEMM output, two fp32 stream buffers, the fp16 LayerNorm output, the attention output,
     // Q | K | V rows, V^T, the MLP hidden activation, the linears' scratch and the fp32 pooled rows
     const size_t b_pa = al256((size_t)Mp * t.Kpad * 2), b_po = al256((size_t)Mp * C * 4), b_x = al256((size_t)M * C * 4),
                  b_h = al256((size_t)M * C * 2), b_qkv = al256((size_t)M * 3 * C * 2), b_vt = al256((size_t)N * C * t.Lkpad * 2),
-                 b_ff = al256((size_t)M * I * 2), b_lin = al256(lin_scratch_bytes(t, M)), b_p32 = al256((size_t)N * C * 4);
-    const size_t need = b_pa + b_po + 2 * b_x + 2 * b_h + b_qkv + b_vt + b_ff + b_lin + b_p32;
+                 b_ff = al256((size_t)M * I * 2), b_lin = al256(lin_scratch_bytes(c.gemm_form, c.hidden_act, M, C, I)),
+                 b_p32 = al256((size_t)N * C * 4);
     bool capturing = false;
     TRY(t.enter(s, &capturing));
-    CTRL_CHECK(!capturing || need <= t.ar.cap, "vision encoder: the first forward of a larger batch allocates its workspace and cannot run "
-                                               "under stream capture -- run it eagerly once, then capture");
-    TRY(t.ar.ensure(need));
+    TRY(t.reserve(b_pa + b_po + 2 * b_x + 2 * b_h + b_qkv + b_vt + b_ff + b_lin + b_p32, capturing, "vision encoder", "batch"));
     char* p = t.ar.base;
+    ClipBufs b;
     half_t* pa = (half_t*)p; p += b_pa;
     float* po = (float*)p; p += b_po;
-    float* xa = (float*)p; p += b_x;
-    float* xb = (float*)p; p += b_x;
-    half_t* h16 = (half_t*)p; p += b_h;
-    half_t* ao = (half_t*)p; p += b_h;
-    half_t* qkv = (half_t*)p; p += b_qkv;
+    b.xa = (float*)p; p += b_x;
+    b.xb = (float*)p; p += b_x;
+    b.h16 = (half_t*)p; p += b_h;
+    b.ao = (half_t*)p; p += b_h;
+    b.qkv = (half_t*)p; p += b_qkv;
     half_t* vt = (half_t*)p; p += b_vt;
-    half_t* ff = (half_t*)p; p += b_ff;
-    LinScratch lws;
-    lws.p = b_lin ? (float*)p : nullptr; lws.bytes = b_lin; p += b_lin;
+    b.ff = (half_t*)p; p += b_ff;
+    b.lws.p = b_lin ? (float*)p : nullptr; b.lws.bytes = b_lin; p += b_lin;
     float* p32 = (float*)p;
-    const size_t esz = odt == DT_F32 ? 4 : 2;
-    auto snap = [&](int k, const float* x) -> int {     // hidden_states[k] = the stream after k layers (0: after pre_layrnorm)
-        if (!hidden || (hidden_index >= 0 && k != hidden_index)) return 0;
-        const size_t slot = hidden_index >= 0 ? 0 : (size_t)k;
-        return op_text_store(x, (char*)hidden + slot * M * C * esz, odt, (size_t)M * C, s);
-    };
-    const int fc1_act = c.hidden_act == 1 ? 3 : 2;
+    const float* xa = b.xa;
+    const ClipSnapshot snap{hidden, hidden_index, odt, (size_t)M * C};     // state 0: after pre_layrnorm
     TRY(op_vision_patchify(px, pdt, N, c.image_size, c.patch_size, mean_std, pa, t.Kpad, s));
-    TRY(pinned(pa, t.patch_w, nullptr, C, t.Kpad, po, DT_F32, Mp, nullptr, 0, s));
-    TRY(op_vision_embed(po, t.cls, t.pos, N, L, C, t.pre_ln.g, t.pre_ln.b, t.layers[0].ln1.g, t.layers[0].ln1.b, eps, xa, h16, s));
-    TRY(snap(0, xa));
+    TRY(pinned_linear(pa, t.patch_w, nullptr, C, t.Kpad, po, DT_F32, Mp, nullptr, 0, s));
+    TRY(op_vision_embed(po, t.cls, t.pos, N, L, C, t.pre_ln.g, t.pre_ln.b, t.layers[0].ln1.g, t.layers[0].ln1.b, eps, b.xa, b.h16, s));
+    TRY(snap(0, xa, s));
     AttnArgs at = {};
-    at.Q = qkv; at.ldq = 3 * C; at.K = qkv + C; at.ldk = 3 * C; at.Vt = vt; at.Lkpad = t.Lkpad; at.kvB = N;
-    at.O = ao; at.ldo = C; at.B = N; at.heads = c.num_attention_heads; at.D = t.D; at.Lq = L; at.Lk = L;
+    at.Q = b.qkv; at.ldq = 3 * C; at.K = b.qkv + C; at.ldk = 3 * C; at.Vt = vt; at.Lkpad = t.Lkpad; at.kvB = N;
+    at.O = b.ao; at.ldo = C; at.B = N; at.heads = c.num_attention_heads; at.D = t.D; at.Lq = L; at.Lk = L;
     at.scale = 1.0f / std::sqrt((float)t.D);
-    for (int i = 0; i < layers; ++i) {
-        const VisionLayer& l = t.layers[i];
-        TRY(run_linear(t, l.qkv, h16, qkv, DT_F16, M, nullptr, 0, lws, s));
-        TRY(op_vision_vt(qkv + 2 * C, 3L * C, vt, N, L, C, t.Lkpad, s));
-        TRY(op_flash_attn(at, s));
-        TRY(run_linear(t, l.out, ao, xb, DT_F32, M, xa, 0, lws, s));
-        TRY(op_layernorm(xb, DT_F32, C, l.ln2.g, l.ln2.b, h16, C, M, C, eps, s));
-        TRY(run_linear(t, l.fc1, h16, ff, DT_F16, M, nullptr, fc1_act, lws, s));
-        TRY(run_linear(t, l.fc2, ff, xa, DT_F32, M, xb, 0, lws, s));
-        TRY(snap(i + 1, xa));
-        if (i + 1 < layers)
-            TRY(op_layernorm(xa, DT_F32, C, t.layers[i + 1].ln1.g, t.layers[i + 1].ln1.b, h16, C, M, C, eps, s));
-    }
+    TRY(run_clip_layers(t.layers, layers, c.gemm_form, c.hidden_act, M, C, eps, b, snap, s, [&] {
+        TRY(op_vision_vt(b.qkv + 2 * C, 3L * C, vt, N, L, C, t.Lkpad, s));
+        return op_flash_attn(at, s);
+    }));
     if (last) TRY(op_text_store(xa, last, odt, (size_t)M * C, s));
     if (pooled || embeds) TRY(op_vision_cls_ln(xa, N, L, C, t.post_ln.g, t.post_ln.b, eps, pooled, odt, p32, s));
     if (embeds) TRY(op_text_proj(p32, t.proj, N, C, c.projection_dim, embeds, odt, s));
@@ -197,63 +134,27 @@ int forward(VisionEncoder& t, const void* px, int pdt, int N, const float* mean_
 
 }  // namespace
 
-#define S(stream) ((hipStream_t)(stream))
-
 extern "C" {
 
 int ctrl_vision_encoder_param_count(const ctrl_vision_encoder_config* cfg) {
-    if (!cfg || validate(*cfg)) return -1;
-    SpecCollector sc; VisionEncoder t;
-    t.cfg = *cfg;
-    derive(t);
-    if (build_vision(sc, t)) return -1;
-    return (int)sc.entries.size();
+    SpecCollector sc;
+    return (cfg && !collect(*cfg, sc)) ? (int)sc.entries.size() : -1;
 }
 
 int ctrl_vision_encoder_param_spec(const ctrl_vision_encoder_config* cfg, int i, char* name, int name_len, int64_t shape[6], int* ndim) {
     CTRL_CHECK(cfg && name && shape && ndim && name_len >= 1, "vision_encoder_param_spec: null argument");
-    TRY(validate(*cfg));
-    SpecCollector sc; VisionEncoder t;
-    t.cfg = *cfg;
-    derive(t);
-    TRY(build_vision(sc, t));
-    CTRL_CHECK(i >= 0 && i < (int)sc.entries.size(), "vision_encoder_param_spec: index out of range");
-    std::strncpy(name, sc.entries[i].name.c_str(), name_len - 1);
-    name[name_len - 1] = 0;
-    *ndim = (int)sc.entries[i].shape.size();
-    for (int k = 0; k < 6; ++k) shape[k] = k < *ndim ? sc.entries[i].shape[k] : 1;
-    return 0;
+    SpecCollector sc;
+    TRY(collect(*cfg, sc));
+    return spec_entry(sc, i, "vision_encoder_param_spec", name, name_len, shape, ndim);
 }
 
 int ctrl_vision_encoder_create(const ctrl_vision_encoder_config* cfg, const ctrl_tensor_ref* tensors, int n_tensors, void* stream,
                                ctrl_vision_encoder** out) {
-    CTRL_CHECK(cfg && out && (tensors || n_tensors == 0), "vision_encoder_create: null argument");
-    *out = nullptr;
-    TRY(validate(*cfg));
-    VisionEncoder* t = new VisionEncoder();
-    t->cfg = *cfg;
-    derive(*t);
-    int rc = t->init_base(n_tensors ? tensors[0].data : nullptr);
-    DeviceGuard dg(t->device);
-    if (!rc) {
-        t->pk = new Packer(tensors, n_tensors, (hipStream_t)stream);
-        rc = build_vision(*t->pk, *t);
-        if (!rc) rc = t->pk->dalloc((size_t)cfg->hidden_size * t->Kpad * sizeof(half_t), (void**)&t->patch_w);
-        if (!rc) rc = op_vision_pack_patch(t->patch32, cfg->hidden_size, t->K, t->Kpad, t->patch_w, (hipStream_t)stream);
-        if (!rc) rc = t->pk->finish();
-    }
-    if (rc) { delete t; return rc; }
-    *out = (ctrl_vision_encoder*)t;
-    return 0;
+    return plan_create<VisionEncoder>("vision_encoder_create", cfg, tensors, n_tensors, stream, (void**)out, validate, build_vision,
+                                      pack_patch_w);
 }
 
-void ctrl_vision_encoder_destroy(ctrl_vision_encoder* h) {
-    if (!h) return;
-    VisionEncoder* t = (VisionEncoder*)h;
-    DeviceGuard dg(t->device);
-    (void)hipDeviceSynchronize();        // queued launches and captured graphs may still address the workspace
-    delete t;
-}
+void ctrl_vision_encoder_destroy(ctrl_vision_encoder* h) { plan_destroy<VisionEncoder>(h); }
 
 int ctrl_vision_encoder_forward(ctrl_vision_encoder* h, const void* pixels, int pixel_dtype, int N, const float* mean_std,
                                 void* last_hidden, void* pooled, void* image_embeds, void* hidden_states, int hidden_index,

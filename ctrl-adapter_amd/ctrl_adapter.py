@@ -13,6 +13,8 @@ _SLOT_F = [1, 1, 1, 2, 2, 2, 4, 4, 4, 8, 8, 8]
 
 
 class ControlNetAdapter(ParamTreeModule):
+    _CREATE, _DESTROY = "ctrl_adapter_create", "ctrl_adapter_destroy"
+
     def __init__(self, backbone_model_name, num_blocks=2, num_frames=8, num_adapters_per_location=3,
                  cross_attention_dim=None, adapter_type="spatial_temporal_resnet_transformer",
                  add_spatial_resnet=True, add_temporal_resnet=False, add_spatial_transformer=True,
@@ -54,22 +56,13 @@ class ControlNetAdapter(ParamTreeModule):
                 ids += sel[k].get(self.num_adapters_per_location, [])
         return ids
 
-    def _destroy(self, plan):
-        L.lib().ctrl_adapter_destroy(plan)
-
     def trim(self):
         """frees the workspace / cache blocks the plan outgrew (see ControlNetModel.trim)"""
         if getattr(self, "_plan", None) is not None:
             L.check(L.lib().ctrl_adapter_trim(self._plan))
 
-    def _ensure_plan(self):
-        if self._plan is None:
-            refs, n, keep = self._tensor_refs()
-            h = C.c_void_p()
-            L.check(L.lib().ctrl_adapter_create(C.byref(self._cfg), refs, n, L.cur_stream(), C.byref(h)))
-            self._plan = h
-            self._note_selection(L.lib().ctrl_adapter_selection)
-        return self._plan
+    def _plan_created(self, slot):
+        self._note_selection(L.lib().ctrl_adapter_selection)
 
     @torch.no_grad()
     def forward(self, down_block_res_samples, mid_block_res_sample=None, sparsity_masking=None, num_frames=None,

@@ -5,8 +5,6 @@ negative prompts encoded in ONE forward.
 
 State-dict keys are the transformers 4.x layout SD-1.5's text_encoder/model.safetensors stores (`text_model.embeddings....`);
 the 5.x layout without the `text_model.` prefix loads as well."""
-import ctypes as C
-
 import torch
 from torch import nn
 
@@ -69,6 +67,8 @@ class _FinalLayerNorm(nn.Module):
 
 
 class CLIPTextModel(ParamTreeModule):
+    _CREATE, _DESTROY = "ctrl_text_encoder_create", "ctrl_text_encoder_destroy"
+
     def __init__(self, vocab_size=49408, hidden_size=512, intermediate_size=2048, projection_dim=512, num_hidden_layers=12,
                  num_attention_heads=8, max_position_embeddings=77, hidden_act="quick_gelu", layer_norm_eps=1e-5,
                  attention_dropout=0.0, initializer_range=0.02, initializer_factor=1.0, pad_token_id=1, bos_token_id=49406,
@@ -108,17 +108,6 @@ class CLIPTextModel(ParamTreeModule):
                 continue
             sd[key if key.startswith("text_model.") else "text_model." + key] = v
         return super().load_state_dict(sd, strict=strict, **k)
-
-    def _destroy(self, plan):
-        L.lib().ctrl_text_encoder_destroy(plan)
-
-    def _ensure_plan(self):
-        if self._plan is None:
-            refs, n, keep = self._tensor_refs()
-            h = C.c_void_p()
-            L.check(L.lib().ctrl_text_encoder_create(C.byref(self._cfg), refs, n, L.cur_stream(), C.byref(h)))
-            self._plan = h
-        return self._plan
 
     def forward(self, input_ids, attention_mask=None, position_ids=None, output_attentions=None, output_hidden_states=False,
                 return_dict=True):
@@ -304,6 +293,7 @@ class CLIPTextModelWithProjection(ParamTreeModule):
     B = 1, even at B = 2 and 2.4x slower at B = 16, profiles/sdxl_text_encoder_bench.txt); both are batch-invariant."""
 
     GEMM_FORM = 0
+    _CREATE, _DESTROY, _CREATE_CFG = "ctrl_text_encoder_create_ext", "ctrl_text_encoder_destroy", ("_cfg", "_ext")
 
     def __init__(self, vocab_size=49408, hidden_size=512, intermediate_size=2048, projection_dim=512, num_hidden_layers=12,
                  num_attention_heads=8, max_position_embeddings=77, hidden_act="quick_gelu", layer_norm_eps=1e-5,
@@ -370,17 +360,6 @@ class CLIPTextModelWithProjection(ParamTreeModule):
                 continue
             sd[key if key.startswith(("text_model.", "text_projection.")) else "text_model." + key] = v
         return super().load_state_dict(sd, strict=strict, **k)
-
-    def _destroy(self, plan):
-        L.lib().ctrl_text_encoder_destroy(plan)
-
-    def _ensure_plan(self):
-        if self._plan is None:
-            refs, n, keep = self._tensor_refs()
-            h = C.c_void_p()
-            L.check(L.lib().ctrl_text_encoder_create_ext(C.byref(self._cfg), C.byref(self._ext), refs, n, L.cur_stream(), C.byref(h)))
-            self._plan = h
-        return self._plan
 
     def forward(self, input_ids, attention_mask=None, position_ids=None, output_attentions=None, output_hidden_states=False,
                 return_dict=True):

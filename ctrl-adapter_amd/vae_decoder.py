@@ -10,26 +10,13 @@ over one set of parameters), a drop-in for `pipe.vae`; and the two pipelines' de
 State-dict keys are diffusers' (`post_quant_conv.weight`, `decoder.conv_in.weight`, ...); a full VAE checkpoint loads into the decoder
 (encoder.* and quant_conv.* are ignored), and so do the legacy attention names (query / key / value / proj_attn).  SVD's
 AutoencoderKLTemporalDecoder is not covered."""
-import ctypes as C
-
 import torch
 
 from . import _lib as L
-from ._plan import Config, ParamTreeModule, c_spec
-from .vae_encoder import _LEGACY_ATTN, AutoencoderKLEncoder, _scaling_factor
+from ._plan import Config, ParamTreeModule, _check_gpu_input, c_spec
+from .vae_encoder import AutoencoderKLEncoder, _check_vae_config, _map_vae_keys, _scaling_factor, _vae_config
 
 _KINDS = (L.VAE_DEC_SAMPLE, L.VAE_DEC_UNIT, L.VAE_DEC_U8)
-
-
-def _dec_config(block_out_channels, layers_per_block, latent_channels, norm_num_groups, out_channels):
-    cfg = L.VaeDecoderConfig()
-    cfg.num_levels = len(block_out_channels)
-    for i, c in enumerate(block_out_channels):
-        cfg.block_out_channels[i] = int(c)
-    cfg.layers_per_block, cfg.latent_channels, cfg.norm_num_groups = layers_per_block, latent_channels, norm_num_groups
-    cfg.norm_eps = 1e-6
-    cfg.out_channels = out_channels
-    return cfg
 
 
 def vae_decoder_spec(cfg):
@@ -47,65 +34,12 @@ class DecoderOutput(tuple):
         return self
 
 
-def _check_decoder_config(who, out_channels, up_block_types, block_out_channels, layers_per_block, act_fn, latent_channels,
-                          norm_num_groups, use_post_quant_conv, mid_block_add_attention):
-    pre = "%s (libctrlhip): " % who
-    if out_channels != 3:
-        raise ValueError(pre + "out_channels must be 3 (got %r)" % (out_channels,))
-    if not 1 <= len(block_out_channels) <= 4:
-        raise ValueError(pre + "block_out_channels must hold 1 to 4 values")
-    if tuple(up_block_types) != ("UpDecoderBlock2D",) * len(block_out_channels):
-        raise ValueError(pre + "up_block_types must all be UpDecoderBlock2D, one per block_out_channels entry (got %r)"
-                         % (tuple(up_block_types),))
-    if norm_num_groups != 32:
-        raise ValueError(pre + "norm_num_groups must be 32 (got %r)" % (norm_num_groups,))
-    if any(c % 32 or not 32 <= c <= 2048 for c in block_out_channels):
-        raise ValueError(pre + "block_out_channels must be multiples of 32 up to 2048 (got %r)" % (block_out_channels,))
-    if not 1 <= latent_channels <= 8:
-        raise ValueError(pre + "latent_channels must be 1 .. 8 (got %r)" % (latent_channels,))
-    if not use_post_quant_conv:
-        raise ValueError(pre + "use_post_quant_conv must be True")
-    if not 1 <= layers_per_block <= 8:
-        raise ValueError(pre + "layers_per_block must be 1 .. 8 (got %r)" % (layers_per_block,))
-    if act_fn != "silu":
-        raise ValueError(pre + "act_fn must be silu (got %r)" % (act_fn,))
-    if not mid_block_add_attention:
-        raise ValueError(pre + "mid_block_add_attention must be True")
-
-
-def _map_vae_keys(state_dict, drop, halves=("decoder",)):
-    """diffusers' keys out of a VAE state dict: keys under the `drop` prefixes left out, the legacy attention names of the mid blocks of
-    `halves` (encoder / decoder) mapped to to_q / to_k / to_v / to_out.0 (a 1 x 1 conv weight of the oldest checkpoints squeezed to the
-    linear's [C][C]); a temporal-decoder checkpoint is refused"""
-    sd = {}
-    legacy = tuple(half + ".mid_block.attentions." for half in halves)
-    for key, v in state_dict.items():
-        if key.startswith("decoder.up_blocks.") and ".spatial_res_block." in key:
-            raise ValueError("this is a temporal-decoder checkpoint (%s): SVD's AutoencoderKLTemporalDecoder is not covered by the "
-                             "libctrlhip KL-VAE decoder" % key)
-        if drop and key.startswith(drop):
-            continue
-        parts = key.split(".")
-        if key.startswith(legacy) and len(parts) >= 6 and parts[4] in _LEGACY_ATTN:
-            key = ".".join(parts[:4] + [_LEGACY_ATTN[parts[4]]] + parts[5:])
-            if v.dim() == 4 and v.shape[2:] == (1, 1):
-                v = v[:, :, 0, 0]
-        sd[key] = v
-    return sd
-
-
 def _run_decoder(m, plan, z, kind, scale, out_dtype, out=None):
     """one ctrl_vae_decoder_forward of the module `m` (its device, dtype, latent_channels, up_factor) with the plan `plan`; `out`: a
     contiguous tensor of the result's shape and dtype to write into (a slice of a larger buffer) instead of a new one"""
-    dev = m.device
-    if dev.type != "cuda":
-        raise RuntimeError("parameters must live on the GPU before the first forward (call .to('cuda')); there is no CPU path")
-    if not z.is_cuda:
-        raise RuntimeError("the latents must live on the GPU; there is no CPU path")
+    dev = _check_gpu_input(m, z, "the latents", "live")
     if z.dim() != 4 or z.shape[1] != m.latent_channels:
         raise ValueError("the latents must be [N, %d, h, w] (got %s)" % (m.latent_channels, tuple(z.shape)))
-    if z.device != dev:
-        raise ValueError("the latents live on %s, the model on %s" % (z.device, dev))
     if kind not in _KINDS:
         raise ValueError("kind must be VAE_DEC_SAMPLE, VAE_DEC_UNIT or VAE_DEC_U8 (got %r)" % (kind,))
     N, _, h, w = z.shape
@@ -136,6 +70,8 @@ class AutoencoderKLDecoder(ParamTreeModule):
     """The decoder of diffusers' AutoencoderKL (its config kwargs; the encoder is AutoencoderKLEncoder, both are AutoencoderKL).  An
     image's pixels are bit-identical alone or inside any batch."""
 
+    _CREATE, _DESTROY = "ctrl_vae_decoder_create", "ctrl_vae_decoder_destroy"
+
     def __init__(self, in_channels=3, out_channels=3, down_block_types=None, up_block_types=None,
                  block_out_channels=(128, 256, 512, 512), layers_per_block=2, act_fn="silu", latent_channels=4, norm_num_groups=32,
                  sample_size=512, scaling_factor=0.18215, shift_factor=None, latents_mean=None, latents_std=None, force_upcast=True,
@@ -145,9 +81,9 @@ class AutoencoderKLDecoder(ParamTreeModule):
         if up_block_types is None:
             up_block_types = ("UpDecoderBlock2D",) * len(block_out_channels)
         self.config = Config({k: v for k, v in locals().items() if k not in ("self", "__class__", "unused")})
-        _check_decoder_config("AutoencoderKLDecoder", out_channels, up_block_types, block_out_channels, layers_per_block, act_fn,
-                              latent_channels, norm_num_groups, use_post_quant_conv, mid_block_add_attention)
-        self._cfg = _dec_config(block_out_channels, layers_per_block, latent_channels, norm_num_groups, out_channels)
+        _check_vae_config("AutoencoderKLDecoder", "decoder", out_channels, up_block_types, block_out_channels, layers_per_block, act_fn,
+                          latent_channels, norm_num_groups, use_post_quant_conv, mid_block_add_attention)
+        self._cfg = _vae_config(block_out_channels, layers_per_block, latent_channels, norm_num_groups, out_channels)
         self.latent_channels = latent_channels
         self.up_factor = 2 ** (len(block_out_channels) - 1)
         self._register_spec(vae_decoder_spec(self._cfg), dtype=torch.float32)
@@ -158,17 +94,6 @@ class AutoencoderKLDecoder(ParamTreeModule):
     def load_state_dict(self, state_dict, strict=True, **k):
         """diffusers' keys of a whole VAE (encoder.* / quant_conv.* dropped), legacy attention names mapped"""
         return super().load_state_dict(_map_vae_keys(state_dict, ("encoder.", "quant_conv.")), strict=strict, **k)
-
-    def _destroy(self, plan):
-        L.lib().ctrl_vae_decoder_destroy(plan)
-
-    def _ensure_plan(self):
-        if self._plan is None:
-            refs, n, keep = self._tensor_refs()
-            h = C.c_void_p()
-            L.check(L.lib().ctrl_vae_decoder_create(C.byref(self._cfg), refs, n, L.cur_stream(), C.byref(h)))
-            self._plan = h
-        return self._plan
 
     def run(self, z, kind=L.VAE_DEC_SAMPLE, scale=1.0, out_dtype=None, out=None):
         """one ctrl_vae_decoder_forward: z [N, lat, h, w] fp32 / fp16 / bf16 on the GPU, multiplied by `scale` on load -> kind
@@ -190,6 +115,8 @@ class AutoencoderKL(AutoencoderKLEncoder):
     encode(x).latent_dist runs the encoder plan, decode(z).sample the decoder plan.  `config.force_upcast` reads False whatever the
     checkpoint says: the fp32 residual stream makes the SDXL pipeline's fp32 round trip (upcast_vae) unnecessary."""
 
+    _WHO = "AutoencoderKL"
+
     def __init__(self, in_channels=3, out_channels=3, down_block_types=None, up_block_types=None,
                  block_out_channels=(128, 256, 512, 512), layers_per_block=2, act_fn="silu", latent_channels=4, norm_num_groups=32,
                  sample_size=512, scaling_factor=0.18215, shift_factor=None, latents_mean=None, latents_std=None, force_upcast=True,
@@ -197,20 +124,17 @@ class AutoencoderKL(AutoencoderKLEncoder):
         boc = tuple(int(c) for c in block_out_channels)
         if up_block_types is None:
             up_block_types = ("UpDecoderBlock2D",) * len(boc)
-        try:
-            super().__init__(in_channels=in_channels, out_channels=out_channels, down_block_types=down_block_types,
-                             up_block_types=up_block_types, block_out_channels=boc, layers_per_block=layers_per_block, act_fn=act_fn,
-                             latent_channels=latent_channels, norm_num_groups=norm_num_groups, sample_size=sample_size,
-                             scaling_factor=scaling_factor, shift_factor=shift_factor, latents_mean=latents_mean,
-                             latents_std=latents_std, force_upcast=force_upcast, use_quant_conv=use_quant_conv,
-                             use_post_quant_conv=use_post_quant_conv, mid_block_add_attention=mid_block_add_attention)
-        except ValueError as e:              # the encoder half's checks speak for this class here
-            raise ValueError(str(e).replace("AutoencoderKLEncoder", "AutoencoderKL", 1)) from None
-        _check_decoder_config("AutoencoderKL", out_channels, up_block_types, boc, layers_per_block, act_fn, latent_channels,
-                              norm_num_groups, use_post_quant_conv, mid_block_add_attention)
+        super().__init__(in_channels=in_channels, out_channels=out_channels, down_block_types=down_block_types,
+                         up_block_types=up_block_types, block_out_channels=boc, layers_per_block=layers_per_block, act_fn=act_fn,
+                         latent_channels=latent_channels, norm_num_groups=norm_num_groups, sample_size=sample_size,
+                         scaling_factor=scaling_factor, shift_factor=shift_factor, latents_mean=latents_mean,
+                         latents_std=latents_std, force_upcast=force_upcast, use_quant_conv=use_quant_conv,
+                         use_post_quant_conv=use_post_quant_conv, mid_block_add_attention=mid_block_add_attention)
+        _check_vae_config("AutoencoderKL", "decoder", out_channels, up_block_types, boc, layers_per_block, act_fn, latent_channels,
+                          norm_num_groups, use_post_quant_conv, mid_block_add_attention)
         self._dec_plan = None
         self.config["force_upcast"] = False
-        self._dec_cfg = _dec_config(boc, layers_per_block, latent_channels, norm_num_groups, out_channels)
+        self._dec_cfg = _vae_config(boc, layers_per_block, latent_channels, norm_num_groups, out_channels)
         self.up_factor = 2 ** (len(boc) - 1)
         enc_spec = self._spec
         dec_spec = vae_decoder_spec(self._dec_cfg)
@@ -228,12 +152,7 @@ class AutoencoderKL(AutoencoderKLEncoder):
         super()._drop_plan()
 
     def _ensure_dec_plan(self):
-        if self._dec_plan is None:
-            refs, n, keep = self._tensor_refs()
-            h = C.c_void_p()
-            L.check(L.lib().ctrl_vae_decoder_create(C.byref(self._dec_cfg), refs, n, L.cur_stream(), C.byref(h)))
-            self._dec_plan = h
-        return self._dec_plan
+        return self._ensure_plan("_dec_plan", "ctrl_vae_decoder_create", ("_dec_cfg",))
 
     def run_decoder(self, z, kind=L.VAE_DEC_SAMPLE, scale=1.0, out_dtype=None, out=None):
         """AutoencoderKLDecoder.run on this module's decoder plan"""

@@ -8,24 +8,78 @@ pipelines' image-latent steps:
 
 State-dict keys are diffusers' (`encoder.conv_in.weight`, ..., `quant_conv.bias`); a full VAE checkpoint loads (decoder.* and
 post_quant_conv.* are ignored), and so do the legacy attention names (query / key / value / proj_attn)."""
-import ctypes as C
-
 import torch
 
 from . import _lib as L
-from ._plan import Config, ParamTreeModule, c_spec
+from ._plan import Config, ParamTreeModule, _check_gpu_input, c_spec
 
 _LEGACY_ATTN = {"query": "to_q", "key": "to_k", "value": "to_v", "proj_attn": "to_out.0"}
 
 
-def _vae_config(block_out_channels, layers_per_block, latent_channels, norm_num_groups):
-    cfg = L.VaeEncoderConfig()
+def _vae_config(block_out_channels, layers_per_block, latent_channels, norm_num_groups, out_channels=None):
+    """the encoder's ctrl_vae_encoder_config, or with out_channels the decoder's ctrl_vae_decoder_config"""
+    cfg = L.VaeEncoderConfig() if out_channels is None else L.VaeDecoderConfig()
     cfg.num_levels = len(block_out_channels)
     for i, c in enumerate(block_out_channels):
         cfg.block_out_channels[i] = int(c)
     cfg.layers_per_block, cfg.latent_channels, cfg.norm_num_groups = layers_per_block, latent_channels, norm_num_groups
     cfg.norm_eps = 1e-6
+    if out_channels is not None:
+        cfg.out_channels = out_channels
     return cfg
+
+
+_HALF_NAMES = {"encoder": ("in_channels", "down_block_types", "DownEncoderBlock2D", "use_quant_conv"),
+               "decoder": ("out_channels", "up_block_types", "UpDecoderBlock2D", "use_post_quant_conv")}
+
+
+def _check_vae_config(who, half, io_channels, block_types, block_out_channels, layers_per_block, act_fn, latent_channels,
+                      norm_num_groups, use_conv, mid_block_add_attention):
+    """what the plan of one half ("encoder" | "decoder") of a KL-VAE covers, refused in the name of the class `who`; io_channels,
+    block_types and use_conv are the half's in / out channels, down / up block types and use_quant_conv / use_post_quant_conv"""
+    pre = "%s (libctrlhip): " % who
+    io_name, types_name, block, conv_name = _HALF_NAMES[half]
+    if io_channels != 3:
+        raise ValueError(pre + "%s must be 3 (got %r)" % (io_name, io_channels))
+    if not 1 <= len(block_out_channels) <= 4:
+        raise ValueError(pre + "block_out_channels must hold 1 to 4 values")
+    if tuple(block_types) != (block,) * len(block_out_channels):
+        raise ValueError(pre + "%s must all be %s, one per block_out_channels entry (got %r)" % (types_name, block, tuple(block_types)))
+    if norm_num_groups != 32:
+        raise ValueError(pre + "norm_num_groups must be 32 (got %r)" % (norm_num_groups,))
+    if any(c % 32 or not 32 <= c <= 2048 for c in block_out_channels):
+        raise ValueError(pre + "block_out_channels must be multiples of 32 up to 2048 (got %r)" % (block_out_channels,))
+    if not 1 <= latent_channels <= 8:
+        raise ValueError(pre + "latent_channels must be 1 .. 8 (got %r)" % (latent_channels,))
+    if not use_conv:
+        raise ValueError(pre + "%s must be True" % conv_name)
+    if not 1 <= layers_per_block <= 8:
+        raise ValueError(pre + "layers_per_block must be 1 .. 8 (got %r)" % (layers_per_block,))
+    if act_fn != "silu":
+        raise ValueError(pre + "act_fn must be silu (got %r)" % (act_fn,))
+    if not mid_block_add_attention:
+        raise ValueError(pre + "mid_block_add_attention must be True")
+
+
+def _map_vae_keys(state_dict, drop, halves=("decoder",)):
+    """diffusers' keys out of a VAE state dict: keys under the `drop` prefixes left out, the legacy attention names of the mid blocks of
+    `halves` (encoder / decoder) mapped to to_q / to_k / to_v / to_out.0 (a 1 x 1 conv weight of the oldest checkpoints squeezed to the
+    linear's [C][C]); with the decoder among `halves` a temporal-decoder checkpoint is refused"""
+    sd = {}
+    legacy = tuple(half + ".mid_block.attentions." for half in halves)
+    for key, v in state_dict.items():
+        if "decoder" in halves and key.startswith("decoder.up_blocks.") and ".spatial_res_block." in key:
+            raise ValueError("this is a temporal-decoder checkpoint (%s): SVD's AutoencoderKLTemporalDecoder is not covered by the "
+                             "libctrlhip KL-VAE decoder" % key)
+        if drop and key.startswith(drop):
+            continue
+        parts = key.split(".")
+        if key.startswith(legacy) and len(parts) >= 6 and parts[4] in _LEGACY_ATTN:
+            key = ".".join(parts[:4] + [_LEGACY_ATTN[parts[4]]] + parts[5:])
+            if v.dim() == 4 and v.shape[2:] == (1, 1):
+                v = v[:, :, 0, 0]
+        sd[key] = v
+    return sd
 
 
 def vae_encoder_spec(cfg):
@@ -100,6 +154,9 @@ class AutoencoderKLEncoder(ParamTreeModule):
     """The encoder of diffusers' AutoencoderKL / AutoencoderKLTemporalDecoder (their config kwargs; the decoder is not built).  An
     image's latents are bit-identical alone or inside any batch."""
 
+    _CREATE, _DESTROY = "ctrl_vae_encoder_create", "ctrl_vae_encoder_destroy"
+    _WHO = "AutoencoderKLEncoder"        # the class a refused configuration is reported for
+
     def __init__(self, in_channels=3, out_channels=3, down_block_types=None, up_block_types=None,
                  block_out_channels=(128, 256, 512, 512), layers_per_block=2, act_fn="silu", latent_channels=4, norm_num_groups=32,
                  sample_size=512, scaling_factor=0.18215, shift_factor=None, latents_mean=None, latents_std=None, force_upcast=True,
@@ -109,28 +166,8 @@ class AutoencoderKLEncoder(ParamTreeModule):
         if down_block_types is None:
             down_block_types = ("DownEncoderBlock2D",) * len(block_out_channels)
         self.config = Config({k: v for k, v in locals().items() if k not in ("self", "__class__", "unused")})
-        if in_channels != 3:
-            raise ValueError("AutoencoderKLEncoder (libctrlhip): in_channels must be 3 (got %r)" % (in_channels,))
-        if not 1 <= len(block_out_channels) <= 4:
-            raise ValueError("AutoencoderKLEncoder (libctrlhip): block_out_channels must hold 1 to 4 values")
-        if tuple(down_block_types) != ("DownEncoderBlock2D",) * len(block_out_channels):
-            raise ValueError("AutoencoderKLEncoder (libctrlhip): down_block_types must all be DownEncoderBlock2D, one per block_out_channels "
-                             "entry (got %r)" % (tuple(down_block_types),))
-        if norm_num_groups != 32:
-            raise ValueError("AutoencoderKLEncoder (libctrlhip): norm_num_groups must be 32 (got %r)" % (norm_num_groups,))
-        if any(c % 32 or not 32 <= c <= 2048 for c in block_out_channels):
-            raise ValueError("AutoencoderKLEncoder (libctrlhip): block_out_channels must be multiples of 32 up to 2048 (got %r)"
-                             % (block_out_channels,))
-        if not 1 <= latent_channels <= 8:
-            raise ValueError("AutoencoderKLEncoder (libctrlhip): latent_channels must be 1 .. 8 (got %r)" % (latent_channels,))
-        if not use_quant_conv:
-            raise ValueError("AutoencoderKLEncoder (libctrlhip): use_quant_conv must be True")
-        if not 1 <= layers_per_block <= 8:
-            raise ValueError("AutoencoderKLEncoder (libctrlhip): layers_per_block must be 1 .. 8 (got %r)" % (layers_per_block,))
-        if act_fn != "silu":
-            raise ValueError("AutoencoderKLEncoder (libctrlhip): act_fn must be silu (got %r)" % (act_fn,))
-        if not mid_block_add_attention:
-            raise ValueError("AutoencoderKLEncoder (libctrlhip): mid_block_add_attention must be True")
+        _check_vae_config(self._WHO, "encoder", in_channels, down_block_types, block_out_channels, layers_per_block, act_fn,
+                          latent_channels, norm_num_groups, use_quant_conv, mid_block_add_attention)
         self._cfg = _vae_config(block_out_channels, layers_per_block, latent_channels, norm_num_groups)
         self.latent_channels = latent_channels
         self.down_factor = 2 ** (len(block_out_channels) - 1)
@@ -142,42 +179,15 @@ class AutoencoderKLEncoder(ParamTreeModule):
     def load_state_dict(self, state_dict, strict=True, **k):
         """diffusers' keys of a whole VAE (decoder.* / post_quant_conv.* dropped), legacy attention names mapped to to_q / to_k / to_v /
         to_out.0 (a 1 x 1 conv weight of the oldest checkpoints squeezed to the linear's [C][C])"""
-        sd = {}
-        for key, v in state_dict.items():
-            if key.startswith(("decoder.", "post_quant_conv.")):
-                continue
-            parts = key.split(".")
-            if key.startswith("encoder.mid_block.attentions.") and len(parts) >= 6 and parts[4] in _LEGACY_ATTN:
-                key = ".".join(parts[:4] + [_LEGACY_ATTN[parts[4]]] + parts[5:])
-                if v.dim() == 4 and v.shape[2:] == (1, 1):
-                    v = v[:, :, 0, 0]
-            sd[key] = v
-        return super().load_state_dict(sd, strict=strict, **k)
-
-    def _destroy(self, plan):
-        L.lib().ctrl_vae_encoder_destroy(plan)
-
-    def _ensure_plan(self):
-        if self._plan is None:
-            refs, n, keep = self._tensor_refs()
-            h = C.c_void_p()
-            L.check(L.lib().ctrl_vae_encoder_create(C.byref(self._cfg), refs, n, L.cur_stream(), C.byref(h)))
-            self._plan = h
-        return self._plan
+        return super().load_state_dict(_map_vae_keys(state_dict, ("decoder.", "post_quant_conv."), ("encoder",)), strict=strict, **k)
 
     def run(self, x, kind=L.VAE_MODE, eps=None, scale=1.0, out_dtype=None):
         """one ctrl_vae_encoder_forward: x [N, 3, H, W] fp32 / fp16 / bf16 on the GPU -> [N, lat, H/f, W/f] (mode: mean * scale;
         sample: (mean + std * eps) * scale) or [N, 4 * lat, H/f, W/f] (moments: mean | logvar | std | var) in out_dtype (default: the
         module's dtype)"""
-        dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("parameters must live on the GPU before the first forward (call .to('cuda')); there is no CPU path")
-        if not x.is_cuda:
-            raise RuntimeError("the image must live on the GPU; there is no CPU path")
+        dev = _check_gpu_input(self, x, "the image")
         if x.dim() != 4 or x.shape[1] != 3:
             raise ValueError("the image must be [N, 3, H, W] (got %s)" % (tuple(x.shape),))
-        if x.device != dev:
-            raise ValueError("the image lives on %s, the model on %s" % (x.device, dev))
         N, _, H, W = x.shape
         f, lat = self.down_factor, self.latent_channels
         if H % 8 or W % 8 or H % f or W % f:

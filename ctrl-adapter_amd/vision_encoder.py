@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from ._plan import Config, ParamTreeModule, c_spec
+from ._plan import Config, ParamTreeModule, _check_gpu_input, c_spec
 
 OPENAI_CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
 OPENAI_CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
@@ -71,6 +71,7 @@ class CLIPVisionModelWithProjection(ParamTreeModule):
     csrc/text_gemm.hip.  Both are batch-invariant: an image's outputs are bit-identical alone or inside any batch."""
 
     GEMM_FORM = 0
+    _CREATE, _DESTROY = "ctrl_vision_encoder_create", "ctrl_vision_encoder_destroy"
 
     def __init__(self, hidden_size=768, intermediate_size=3072, projection_dim=512, num_hidden_layers=12, num_attention_heads=12,
                  num_channels=3, image_size=224, patch_size=32, hidden_act="quick_gelu", layer_norm_eps=1e-5, attention_dropout=0.0,
@@ -127,27 +128,12 @@ class CLIPVisionModelWithProjection(ParamTreeModule):
         sd = {key: v for key, v in state_dict.items() if not key.endswith("embeddings.position_ids")}
         return super().load_state_dict(sd, strict=strict, **k)
 
-    def _destroy(self, plan):
-        L.lib().ctrl_vision_encoder_destroy(plan)
-
-    def _ensure_plan(self):
-        if self._plan is None:
-            refs, n, keep = self._tensor_refs()
-            h = C.c_void_p()
-            L.check(L.lib().ctrl_vision_encoder_create(C.byref(self._cfg), refs, n, L.cur_stream(), C.byref(h)))
-            self._plan = h
-        return self._plan
-
     def run(self, pixels, mean_std=None, last=False, pooled=False, embeds=True, hidden_index=None, out_dtype=None):
         """one ctrl_vision_encoder_forward: pixels on the GPU, [N][3][S][S] fp32 / fp16 / bf16 or uint8 [N][S][S][3] (read as x / 255);
         mean_std = (mean[3], std[3]) normalises them in fp32 inside the patch kernel (None: already normalised).  Returns (last, pooled,
         embeds, hidden) in out_dtype (default: the model's dtype), None where not asked; hidden_index None = no state, -1 = all
         [layers + 1][N][L][C], k = state k [N][L][C] (with nothing else asked the layers after k are not run)"""
-        dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("parameters must live on the GPU before the first forward (call .to('cuda')); there is no CPU path")
-        if not pixels.is_cuda:
-            raise RuntimeError("pixel_values must live on the GPU; there is no CPU path")
+        dev = _check_gpu_input(self, pixels, "pixel_values", "live")
         S = self.config.image_size
         if pixels.dtype == torch.uint8:
             if pixels.dim() != 4 or tuple(pixels.shape[1:]) != (S, S, 3):
@@ -157,8 +143,6 @@ class CLIPVisionModelWithProjection(ParamTreeModule):
             if pixels.dim() != 4 or tuple(pixels.shape[1:]) != (3, S, S):
                 raise ValueError("pixel_values must be [N, 3, %d, %d] (got %s)" % (S, S, tuple(pixels.shape)))
             pdt = L.dtype_code(pixels.dtype)
-        if pixels.device != dev:
-            raise ValueError("pixel_values live on %s, the model on %s" % (pixels.device, dev))
         px = pixels.contiguous()
         N = px.shape[0]
         cfg = self.config
