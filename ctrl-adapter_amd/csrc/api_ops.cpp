@@ -16,6 +16,10 @@ int ctrl_op_igemm_pinned(const ctrl_igemm_desc* d, void* stream) {
 int ctrl_igemm_splitk_factor(const ctrl_igemm_desc* d) { return d ? igemm_splitk_factor(*d) : 0; }
 int64_t ctrl_igemm_splitk_ws_bytes(const ctrl_igemm_desc* d, int splits) { return d ? (int64_t)igemm_splitk_ws_bytes(*d, splits) : 0; }
 int64_t ctrl_igemm_splitk_ticket_words(const ctrl_igemm_desc* d, int splits) { return d ? (int64_t)igemm_splitk_ticket_words(*d, splits) : 0; }
+int ctrl_igemm_select(const ctrl_igemm_desc* d, int group_n, int pinned, char* buf, int cap) {
+    CTRL_CHECK(d != nullptr, "igemm_select: null descriptor");
+    return igemm_select_text(*d, group_n, pinned != 0, buf, cap);
+}
 int ctrl_op_ffn(const ctrl_ffn_desc* d, void* stream) {
     CTRL_CHECK(d != nullptr, "ffn: null descriptor");
     return op_ffn_fused_group(d, 1, S(stream));

@@ -871,102 +871,24 @@ OrderSpec parse_order(const char* t) {
 // its weight panels in groups of <= 1 MiB under the legacy XCD split of the rows: 0.844 -> 0.786 ms at M = 131072, results
 // bit-identical; the same walk is neutral on the other wide GEMMs of the path (M = 32768 and the ControlNet's GEGLUs), and
 // splitting the weight panels over the XCDs instead ("n,G") never won.  Everything else keeps the legacy walk.
-int plan_order(const IGemmArgs& a, int BM, int BN, int ntm, int ntn) {
+int plan_order(const IGemmArgs& a, bool wide, int BN, int ntm, int ntn) {
     if (g_order_spec.kind == -1) {
         const char* e = policy_raw(P_IGEMM_ORDER);
         g_order_spec = e ? parse_order(e) : OrderSpec{1, 0, 0};
         if (g_order_spec.kind == -2) { fprintf(stderr, "ctrl: CTRL_IGEMM_ORDER not understood, using auto\n"); g_order_spec = {1, 0, 0}; }
     }
-    (void)BM;
     const OrderSpec sp = g_order_spec;
     if (sp.kind == 0) return 0;
     if (sp.kind == 2) return tileorder::make_order(sp.mode, sp.group);
-    if (a.mode != IG_ROWS || (ntm & 7) != 0) return 0;
+    // The 8-phase wide tiles: the legacy walk (every XCD a contiguous range of the M-major list) unless an order is forced.  The grouped
+    // weight-panel walk that pays for the BK = 32 kernels re-fetches every activation panel once per group, and at this kernel's
+    // rate that traffic is the limiter: M131072 N2048 K2048 1.52 ms grouped vs 1.07 ms legacy (profiles/r04_gemm_tile_order_8phase.txt)
+    if (wide || a.mode != IG_ROWS || (ntm & 7) != 0) return 0;
     const double panel = (double)BN * a.Ktot * 2.0, weights = (double)a.Nout * a.Ktot * 2.0;      // bytes
     if (weights <= 2.0 * 1024 * 1024) return 0;
     int G = (int)(1024.0 * 1024.0 / panel);
     if (G < 1) G = 1;
     return G < ntn ? tileorder::make_order(tileorder::ORDER_XCD_M, G) : 0;
-}
-
-// descriptors of the grouped launch being dispatched (op_igemm_group): [0] is the problem the dispatcher sees
-thread_local const IGemmArgs* t_grp = nullptr;
-thread_local int t_grp_n = 1;
-inline int grp_count() { return t_grp ? t_grp_n : 1; }
-inline const IGemmArgs& grp_at(const IGemmArgs& a, int i) { return t_grp ? t_grp[i] : a; }
-// workgroups per problem of a launch: a group pads them to a multiple of 8 (XCD of a workgroup = its local index % 8, tile_order.h)
-inline int grp_per(int nblk) { return grp_count() > 1 ? ((nblk + 7) & ~7) : nblk; }
-// split-K in the finish-kernel form: the GEMM writes fp32 row slabs, every epilogue term is applied once by the finish kernel
-inline IGemmArgs splitk_slab_desc(const IGemmArgs& a) {
-    IGemmArgs p = a;
-    p.bias = nullptr; p.rowvec = nullptr; p.res = nullptr; p.res_f32 = 0; p.act = 0; p.scale = 1.f; p.out16 = nullptr;
-    p.blend_mix = nullptr; p.blend_x = nullptr;
-    p.nseg = 1;
-    p.seg[0] = IGemmSeg{a.splitk_ws, a.Nout, 0, a.Nout, SEG_ROW, DT_F32, 1, 0};
-    return p;
-}
-int launch_splitk_finish(const IGemmArgs& a, int splitk, hipStream_t s) {
-    for (int i = 0; i < grp_count(); ++i) {
-        const IGemmArgs& ai = grp_at(a, i);
-        const size_t total = (size_t)ai.M * (ai.Nout / 8);
-        size_t blocks = (total + 255) / 256;
-        if (blocks > 4096) blocks = 4096;
-        PROF_WORK(0, 4.0 * splitk * ai.M * ai.Nout);
-        prof_detail("M%d N%d splitk%d", ai.M, ai.Nout, splitk);
-        LAUNCH("splitk_finish", splitk_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, s, ai, (const float*)ai.splitk_ws, splitk);
-    }
-    return 0;
-}
-void prof_igemm(const IGemmArgs& a, const char* extra) {
-    const int G = grp_count();
-    // algorithmic work = the reference op's: a split operand doubles the K the kernel walks, not the FLOPs that count
-    const double kalg = a.a_split ? 0.5 * a.Ktot : (double)a.Ktot;
-    PROF_WORK(G * 2.0 * a.M * a.Nout * kalg, G * 2.0 * ((double)a.M * a.Cin + (double)a.Nout * a.Ktot + (double)a.M * a.Nout));
-    char grp[16] = "";
-    if (G > 1) snprintf(grp, sizeof(grp), " x%d", G);
-    prof_detail("M%d N%d K%d taps%d%s%s%s%s", a.M, a.Nout, a.Ktot, a.taps, a.a_split ? " split-A" : "", a.geglu ? " geglu" : "", extra, grp);
-}
-
-template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int NSTAGE, int MODE, bool SWAP>
-int launch_cfg2(const IGemmArgs& a, hipStream_t s, int splitk = 1) {
-    constexpr int PASSROWS = WAVES_M * WAVES_N * (64 / (BK / 8));
-    constexpr int BNP = (BN + PASSROWS - 1) / PASSROWS * PASSROWS;
-    constexpr size_t ring = (size_t)NSTAGE * (BM + BNP) * BK * sizeof(half_t);
-    constexpr int stage_w = (BN / WAVES_N) > (BM / WAVES_M) ? (BN / WAVES_N) : (BM / WAVES_M);     // row / transposed staging
-    constexpr size_t stage_bytes = (size_t)WAVES_M * WAVES_N * 16 * (stage_w + 4) * sizeof(float);
-    constexpr size_t smem = ring > stage_bytes ? ring : stage_bytes;
-    static bool attr_done[kMaxDevices] = {};       // function attributes are per device
-    const int dev = cur_device();
-    if (!attr_done[dev]) {
-        HIP_TRY(hipFuncSetAttribute((const void*)igemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, NSTAGE, MODE, SWAP>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_done[dev] = true;
-    }
-    const half_t* zeros = zero_page();
-    CTRL_CHECK(zeros != nullptr, "igemm: could not allocate the zero page");
-    const int ntm = (a.M + BM - 1) / BM, ntn = (a.Nout + BN - 1) / BN;
-    const int order = plan_order(a, BM, BN, ntm, ntn);
-    const int G = grp_count();
-    const int per = grp_per(ntm * ntn * splitk);
-    const char* tag = MODE == IG_ROWS ? "igemm_rows" : (MODE == IG_CONV2D ? "igemm_conv" : "igemm_temporal");
-    const auto sym = [&]() { prof_symbol("igemm_kernel<%d, %d, %d, %d, %d, %d, %d, %s>", BM, BN, BK, WAVES_M, WAVES_N, NSTAGE, MODE, SWAP ? "true" : "false"); };
-    IGemmGroup grp;
-    if (splitk > 1) {
-        // partial sums go to fp32 slabs [splitk][M][Nout]; every epilogue term is applied once, by the finish kernel
-        for (int i = 0; i < G; ++i) grp.a[i] = splitk_slab_desc(grp_at(a, i));
-        char ex[32]; snprintf(ex, sizeof(ex), " splitk%d", splitk);
-        prof_igemm(a, ex);
-        sym();
-        LAUNCH(tag, (igemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, NSTAGE, MODE, SWAP>), dim3(per * G),
-               dim3(WAVES_M * WAVES_N * 64), smem, s, grp, per, ntm, ntn, zeros, splitk, order);
-        return launch_splitk_finish(a, splitk, s);
-    }
-    for (int i = 0; i < G; ++i) grp.a[i] = grp_at(a, i);
-    prof_igemm(a, "");
-    sym();
-    LAUNCH(tag, (igemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, NSTAGE, MODE, SWAP>), dim3(per * G), dim3(WAVES_M * WAVES_N * 64), smem, s,
-           grp, per, ntm, ntn, zeros, 1, order);
-    return 0;
 }
 
 // Aligned row-major outputs and single aligned transposed (NCHW / V^T) outputs use the swapped-operand kernel (LDS-staged
@@ -992,7 +914,8 @@ bool can_swap(const IGemmArgs& a) {
     return swap;
 }
 
-// the 8-phase wide-tile kernel (igemm8_kernel) can take this problem: swapped epilogue, whole 64-deep k-tiles per tap, 32-bit offsets
+// the 8-phase wide-tile kernel (igemm8_kernel) can take this problem: swapped epilogue (`swap` = can_swap(a)), whole 64-deep k-tiles per
+// tap, 32-bit offsets
 // CTRL_IGEMM8: "0" never, "force" whenever the problem is eligible (any grid size: the parity tests run their small shapes
 // through it this way), default = where the grid fills the chip
 int g_igemm8_mode = -1;
@@ -1001,8 +924,8 @@ int igemm8_mode() {
     const char* e = policy_raw(P_IGEMM8);
     return !e ? 1 : (e[0] == '0' ? 0 : (!strcmp(e, "force") ? 2 : 1));
 }
-bool can_use8(const IGemmArgs& a) {
-    if (!igemm8_mode() || !can_swap(a)) return false;
+bool can_use8(const IGemmArgs& a, bool swap) {
+    if (!igemm8_mode() || !swap) return false;
     if (a.Cin % 64 != 0 || (a.a_split == 2 && ((a.Cin / 2) % 64 != 0 || a.mode == IG_TEMPORAL))) return false;
     // conv rows are packed as image (8 bits) | y + 1 (12 bits) | x + 1 (12 bits)
     if (a.mode == IG_CONV2D && ((double)a.M / ((double)a.Hout * a.Wout) > 256.0 || a.Hin * a.up > 4000 || a.Win * a.up > 4000 ||
@@ -1014,76 +937,314 @@ bool can_use8(const IGemmArgs& a) {
     return abytes < 2147483648.0 && (double)a.Nout * a.Ktot * 2.0 < 2147483648.0;
 }
 
-template <int NI, int MODE>
-int launch8(const IGemmArgs& a, hipStream_t s, int splitk = 1) {
-    constexpr int BM = 256, BN = 64 * NI;
+// first column of the transposed last segment of a MIXED segment list on the vector epilogue (0 = not such a problem): every tile must
+// lie in one segment, so only tile widths that divide it may be chosen
+int mixed_boundary(const IGemmArgs& a, bool swap) {
+    if (a.nseg < 2 || a.seg[a.nseg - 1].fmt != SEG_TRANSPOSED || !swap) return 0;
+    return a.seg[a.nseg - 1].col_begin;
+}
+
+// ---- split-K geometry: what the selector, the launcher and the sizing queries (igemm_splitk_*) agree on ----
+// split-K runs on the wide (256-row) tiles only: 320 columns where they divide Nout, 256 otherwise
+inline int wide_bn(const IGemmArgs& a) { return (a.Nout % 320 == 0) ? 320 : 256; }
+inline size_t wide_tiles(const IGemmArgs& a) { return (size_t)((a.M + 255) / 256) * ((a.Nout + wide_bn(a) - 1) / wide_bn(a)); }
+inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
+// finish-kernel form: fp32 row slabs [splitk][M][Nout]
+inline size_t splitk_rows_bytes(const IGemmArgs& a, int sk) { return (size_t)sk * a.M * a.Nout * sizeof(float); }
+// in-launch form: tile-shaped fragment slabs [tile][split][fragment][thread], then (at the next multiple of 256 bytes, for callers that
+// do not hand in their own) the ticket words: one per tile for 2..4 splits, five for the two-level reduction of 5..16 splits (see the kernel)
+inline size_t splitk_frag_bytes(const IGemmArgs& a, int sk) { return wide_tiles(a) * sk * 256 * wide_bn(a) * sizeof(float); }
+inline size_t splitk_twords(const IGemmArgs& a, int sk) { return wide_tiles(a) * (sk > 4 ? 5 : 1); }
+
+// number of K splits for this problem (1 = none); `use8` = can_use8(a)
+int splitk_factor(const IGemmArgs& a, bool use8) {
+    if (a.geglu || a.nseg != 1 || a.seg[0].fmt != SEG_ROW || a.Nout % 64 != 0 || a.Cin % 32 != 0 || a.mode == IG_TEMPORAL) return 1;
+    if (a.Nout % wide_bn(a) != 0) return 1;
+    const long tiles = (long)wide_tiles(a);
+    const int nk32 = a.Ktot / 32;
+    if (tiles >= 160 || nk32 < 64) return 1;
+    int sk = (int)((256 + tiles - 1) / tiles);
+    if (sk > 16) sk = 16;
+    while (sk > 1 && nk32 / sk < 16) --sk;
+    // The kernels give split s the k-tiles [s * per, (s + 1) * per) with per = ceil(nk / sk) -- rounded up to even for the paired
+    // split-operand walk, which never cuts a (hi, lo) pair -- in THEIR k-tile depth: 64 for the 8-phase kernel, 32 for the ring kernel.
+    // Pick sk such that the last split still has work in the depth of the kernel that will run (ADVICE r2 / r4: 640 -> 640 3x3 at 24
+    // tiles: nk64 = 90, sk = 11, per = 9 left split 10 empty -- an idle workgroup whose prologue DMA started at k = Ktot)
+    const int depth = use8 ? 64 : 32;
+    const int nk = a.Ktot / depth;
+    auto per_of = [&](int f) { int p = (nk + f - 1) / f; if (a.a_split == 2) p = (p + 1) & ~1; return p; };
+    while (sk > 1 && (long)(sk - 1) * per_of(sk) >= nk) --sk;
+    return sk;
+}
+
+// ---- the kernel forms ----
+// THE list of instantiated tiles; every entry exists in the three gather modes.
+//   W(id, NI)                                                    the 8-phase wide tile, 256 x 64 NI x 64 (vector epilogue)
+//   R(id, force, BM, BN, BK, WAVES_M, WAVES_N, NSTAGE)           a ring tile in the SWAP = true form (vector epilogue) only
+//   B(id, force, BM, BN, BK, WAVES_M, WAVES_N, NSTAGE)           a ring tile with both epilogues: entry id (vector), then id + 1 (scalar)
+// `force` is the tile's CTRL_IGEMM_FORCE name (tools/tile_experiment.py), nullptr = it has none.
+#define IGEMM_TILES(W, R, B)                                  \
+    W(W5, 5)                                                  \
+    W(W4, 4)                                                  \
+    R(T256x320, nullptr, 256, 320, 32, 2, 4, 4)               \
+    R(T256x256, nullptr, 256, 256, 32, 2, 4, 4)               \
+    B(T128x128x32, "128x128x32", 128, 128, 32, 2, 2, 3)       \
+    B(T128x64x64, "128x64x64", 128, 64, 64, 2, 2, 3)          \
+    B(T64x64x64, "64x64x64", 64, 64, 64, 2, 2, 3)             \
+    B(T128x128x64, "128x128x64", 128, 128, 64, 2, 4, 4)       \
+    R(T128x256, "128x256", 128, 256, 32, 2, 4, 3)             \
+    R(T256x128, "256x128", 256, 128, 32, 4, 2, 3)             \
+    R(T4w256x128, "4w256x128", 256, 128, 32, 2, 2, 3)         /* 4 waves x 256 registers, two workgroups per CU */ \
+    R(T4w128x256, "4w128x256", 128, 256, 32, 1, 4, 3)         \
+    B(T64x64x32, nullptr, 64, 64, 32, 2, 2, 3)
+
+struct Tile {
+    int ni;                                   // 8-phase kernel: BN / 64; 0 = the ring kernel
+    int bm, bn, bk, wm, wn, nstage;           // (wm, wn, nstage: ring kernel)
+    bool swap;
+    const char* force;
+    int threads;
+    size_t smem;                              // dynamic LDS
+    const void* kern[3];                      // by gather mode (IG_ROWS, IG_CONV2D, IG_TEMPORAL)
+};
+template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int NSTAGE>
+constexpr size_t ring_smem() {
+    constexpr int PASSROWS = WAVES_M * WAVES_N * (64 / (BK / 8));
+    constexpr int BNP = (BN + PASSROWS - 1) / PASSROWS * PASSROWS;
+    constexpr size_t ring = (size_t)NSTAGE * (BM + BNP) * BK * sizeof(half_t);
+    constexpr int stage_w = (BN / WAVES_N) > (BM / WAVES_M) ? (BN / WAVES_N) : (BM / WAVES_M);     // row / transposed staging
+    constexpr size_t stage_bytes = (size_t)WAVES_M * WAVES_N * 16 * (stage_w + 4) * sizeof(float);
+    return ring > stage_bytes ? ring : stage_bytes;
+}
+template <int NI>
+constexpr size_t wide_smem() {
     constexpr size_t ring = g8::Lds<NI>::TOTAL;
     constexpr int stage_w = 128 > 16 * NI ? 128 : 16 * NI;                                            // row / transposed staging of the shared epilogue
     constexpr size_t stage_bytes = (size_t)8 * 16 * (stage_w + 4) * sizeof(float);
-    constexpr size_t smem = ring > stage_bytes ? ring : stage_bytes;
-    static bool attr_done[kMaxDevices] = {};
-    const int dev = cur_device();
-    if (!attr_done[dev]) {
-        HIP_TRY(hipFuncSetAttribute((const void*)igemm8_kernel<NI, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_done[dev] = true;
-    }
-    const int ntm = (a.M + BM - 1) / BM, ntn = (a.Nout + BN - 1) / BN;
-    // Tile walk: the legacy one (every XCD a contiguous range of the M-major list) unless an order is forced.  The grouped
-    // weight-panel walk that pays for the BK = 32 kernels re-fetches every activation panel once per group, and at this kernel's
-    // rate that traffic is the limiter: M131072 N2048 K2048 1.52 ms grouped vs 1.07 ms legacy (profiles/r04_gemm_tile_order_8phase.txt)
-    (void)plan_order(a, BM, BN, ntm, ntn);          // (parses CTRL_IGEMM_ORDER on first use)
-    const int order = g_order_spec.kind == 2 ? tileorder::make_order(g_order_spec.mode, g_order_spec.group) : 0;
-    const int G = grp_count();
-    const int per = grp_per(ntm * ntn * splitk);
-    const char* tag = MODE == IG_ROWS ? "igemm_rows" : (MODE == IG_CONV2D ? "igemm_conv" : "igemm_temporal");
-    const auto sym = [&]() { prof_symbol("igemm8_kernel<%d, %d>", NI, MODE); };
-    IGemmGroup grp;
-    if (splitk > 1) {
-        // 2..4 splits: reduced inside the launch by the last-arriving workgroup of every tile (see the kernel); the workspace then
-        // holds tile-shaped fragment slabs [tile][split][fragment][thread] + one ticket word per tile (zeroed by a memset node)
-        const size_t slabs = (size_t)ntm * ntn * splitk * BM * BN * sizeof(float);
-        const bool own_tickets = a.splitk_tickets != nullptr;       // (igemm_same_form: all of the group or none)
-        const size_t twords = (size_t)ntm * ntn * (splitk > 4 ? 5 : 1);      // ticket words: see the kernel
-        const size_t need = own_tickets ? slabs : (slabs + 255) / 256 * 256 + twords * sizeof(int);
-        // CTRL_SPLITK_INLAUNCH: 0 = always the finish kernel; default = in-launch for 2..4 splits; "all" = also the two-level form for 5..16
-        // splits -- built and measured in round 6, NOT the default: the last arrivers read their <= 4 slabs of 256-320 KB alone, at the
-        // 60-120 GB/s one workgroup gets (MI355X_MICROARCH.md "handoff-payload"), twice; M512 N1280 K11520 x15: 52 + 14 us (GEMM + finish
-        // kernel over the whole chip) -> 128 us, the ControlNet 8.16 -> 9.14 ms (profiles/r06_splitk_two_level.txt)
-        const char* const il = policy_raw(P_SPLITK_INLAUNCH);
-        const int inlaunch = (il && il[0] == '0') ? 0 : 1;
-        const int inlaunch_max = (il && il[0] == 'a') ? 16 : 4;
-        bool fits = true;
-        for (int i = 0; i < G; ++i) fits = fits && (size_t)grp_at(a, i).splitk_ws_bytes >= need;
-        if (inlaunch && splitk <= inlaunch_max && fits) {
-            const long red_off = own_tickets ? -2L : (long)((slabs + 255) / 256 * 256);
-            for (int i = 0; i < G; ++i) {
-                grp.a[i] = grp_at(a, i);
-                // ticket words: the caller's zeroed ones, or the tail of the scratch, zeroed here (a kernel node: see op_fill_zero)
-                if (!own_tickets) TRY(op_fill_zero((char*)grp.a[i].splitk_ws + red_off, twords * sizeof(int), s));
-            }
-            char ex[40]; snprintf(ex, sizeof(ex), " splitk%d in-launch", splitk);
-            prof_igemm(a, ex);
-            sym();
-            LAUNCH(tag, (igemm8_kernel<NI, MODE>), dim3(per * G), dim3(512), smem, s, grp, per, ntm, ntn, splitk, order, red_off);
-            return 0;
+    return ring > stage_bytes ? ring : stage_bytes;
+}
+#define TILE_ID_W(id, NI) id,
+#define TILE_ID_R(id, ...) id,
+#define TILE_ID_B(id, ...) id, id##_scalar,
+enum TileId { IGEMM_TILES(TILE_ID_W, TILE_ID_R, TILE_ID_B) kNumTiles };
+#define RING_KERN(MODE, SWAP, ...) (const void*)igemm_kernel<__VA_ARGS__, MODE, SWAP>
+#define TILE_RING(force, SWAP, BM, BN, BK, WM, WN, NS)                                                               \
+    {0, BM, BN, BK, WM, WN, NS, SWAP, force, WM * WN * 64, ring_smem<BM, BN, BK, WM, WN, NS>(),                      \
+     {RING_KERN(IG_ROWS, SWAP, BM, BN, BK, WM, WN, NS), RING_KERN(IG_CONV2D, SWAP, BM, BN, BK, WM, WN, NS),         \
+      RING_KERN(IG_TEMPORAL, SWAP, BM, BN, BK, WM, WN, NS)}},
+#define TILE_W(id, NI)                                                                                               \
+    {NI, 256, 64 * NI, 64, 0, 0, 0, true, nullptr, 512, wide_smem<NI>(),                                             \
+     {(const void*)igemm8_kernel<NI, IG_ROWS>, (const void*)igemm8_kernel<NI, IG_CONV2D>, (const void*)igemm8_kernel<NI, IG_TEMPORAL>}},
+#define TILE_R(id, force, ...) TILE_RING(force, true, __VA_ARGS__)
+#define TILE_B(id, force, ...) TILE_RING(force, true, __VA_ARGS__) TILE_RING(force, false, __VA_ARGS__)
+const Tile kTiles[kNumTiles] = {IGEMM_TILES(TILE_W, TILE_R, TILE_B)};
+static_assert(IG_ROWS == 0 && IG_CONV2D == 1 && IG_TEMPORAL == 2, "Tile::kern is indexed by the gather mode");
+
+// ---- selection: everything that is decided about a launch, decided in one place and without a device ----
+enum { RED_NONE = 0, RED_FINISH = 1, RED_INLAUNCH = 2 };
+struct IGemmForm {
+    int tile;              // TileId: kernel family, tile, waves, NSTAGE / NI and SWAP (kTiles); -1 = no form (igemm_select: pinned)
+    int splitk;            // K splits (1 = none)
+    int reduce;            // RED_FINISH: fp32 row slabs, every epilogue term applied once by splitk_finish_kernel; RED_INLAUNCH: reduced inside
+                           // the launch by the last-arriving workgroup of every tile (8-phase kernel; see there)
+    bool own_tickets;      // RED_INLAUNCH: the ticket words are the caller's zeroed splitk_tickets; else the tail of the scratch, zeroed by the launch
+    int order;             // tile walk (tile_order.h)
+};
+
+// The form op_igemm gives the problem `a` as one of `group_n` same-form problems of a launch (a plain launch: 1).  Pure: it reads the
+// descriptor, the policy table and the test overrides (igemm_set_wide / igemm_set_order) and touches no device.
+// pinned: the one fixed form of the encoder plans (op_igemm_pinned), tile -1 where the problem cannot take it.
+IGemmForm igemm_select(const IGemmArgs& a, int group_n, bool pinned = false) {
+    const bool rows = a.mode == IG_ROWS, bk64 = (a.Cin % 64) == 0;
+    const bool swap = can_swap(a), use8 = can_use8(a, swap);
+    const int wide = wide_bn(a) == 320 ? W5 : W4;
+    const int mb = mixed_boundary(a, swap);
+    auto al = [&](int bn) { return mb == 0 || mb % bn == 0; };
+    auto form = [&](int t, int sk = 1) {
+        const Tile& T = kTiles[t];
+        IGemmForm f = {t, sk, RED_NONE, false, plan_order(a, T.ni != 0, T.bn, (a.M + T.bm - 1) / T.bm, (a.Nout + T.bn - 1) / T.bn)};
+        if (sk > 1) {
+            // CTRL_SPLITK_INLAUNCH: 0 = always the finish kernel; default = in-launch for 2..4 splits; "all" = also the two-level form for 5..16
+            // splits -- built and measured in round 6, NOT the default: the last arrivers read their <= 4 slabs of 256-320 KB alone, at the
+            // 60-120 GB/s one workgroup gets (MI355X_MICROARCH.md "handoff-payload"), twice; M512 N1280 K11520 x15: 52 + 14 us (GEMM + finish
+            // kernel over the whole chip) -> 128 us, the ControlNet 8.16 -> 9.14 ms (profiles/r06_splitk_two_level.txt)
+            const char* const il = policy_raw(P_SPLITK_INLAUNCH);
+            const int inlaunch_max = (il && il[0] == '0') ? 0 : ((il && il[0] == 'a') ? 16 : 4);
+            f.own_tickets = a.splitk_tickets != nullptr;       // (igemm_same_form: all of a group or none, and one scratch size)
+            const size_t need = f.own_tickets ? splitk_frag_bytes(a, sk) : align256(splitk_frag_bytes(a, sk)) + splitk_twords(a, sk) * sizeof(int);
+            f.reduce = (T.ni && sk <= inlaunch_max && (size_t)a.splitk_ws_bytes >= need) ? RED_INLAUNCH : RED_FINISH;
         }
-        for (int i = 0; i < G; ++i) grp.a[i] = splitk_slab_desc(grp_at(a, i));
-        char ex[32]; snprintf(ex, sizeof(ex), " splitk%d", splitk);
-        prof_igemm(a, ex);
-        sym();
-        LAUNCH(tag, (igemm8_kernel<NI, MODE>), dim3(per * G), dim3(512), smem, s, grp, per, ntm, ntn, splitk, order, (long)-1);
-        return launch_splitk_finish(a, splitk, s);
+        return f;
+    };
+    auto either = [&](int t) { return form(swap ? t : t + 1); };      // B tiles: launch_cfg's choice of the epilogue by can_swap()
+    // One fixed form for the text encoder (plan_text.cpp): the 64 x 64 x 64 tile at every M, never split-K, never grouped -- every output row
+    // is then computed by the same instruction sequence whatever the batch, so a prompt encodes to the same bits alone or inside a batch
+    // (the ladder below sizes the tile by M).  Row-major problems with Cin % 64 == 0 and the aligned vector epilogue only.
+    if (pinned) return (rows && bk64 && !a.geglu && swap) ? form(T64x64x64) : IGemmForm{-1, 1, RED_NONE, false, 0};
+    // Tile choice: 256x128 (8 waves) when the grid still over-fills the 256 CUs, 128x128 otherwise, 64x64 for small
+    // problems.  N extents that are not multiples of 128 pay padded columns, so the waste is weighed against tile size.
+    // (a grouped launch fills the chip with all its problems: the tile is sized for the group, unless the caller wants every problem
+    // computed with the tile it would get alone -- ctrl_group_launches(2), bit-identical to one-by-one launches)
+    const long gmul = group_tiles_as_alone() ? 1 : group_n;
+    auto tiles = [&](int bm, int bn) { return gmul * (long)((a.M + bm - 1) / bm) * ((a.Nout + bn - 1) / bn); };
+    auto eff = [&](int bn) { return (double)a.Nout / (double)(((a.Nout + bn - 1) / bn) * bn); };
+    // 256x256 (8 waves, 128x64 per wave): fewest LDS bytes per FLOP -- the limiter of the smaller tiles on this chip
+    // split-K: small-M / long-K problems (the ControlNet's low-resolution 3x3 convs) leave most CUs idle with 256-row
+    // tiles and run far below MFMA speed with small tiles; splitting the reduction fills the chip with the wide tile
+    {
+        const int sk = (a.splitk_ws && swap) ? splitk_factor(a, use8) : 1;
+        if (sk > 1 && (size_t)a.splitk_ws_bytes >= splitk_rows_bytes(a, sk) && (((uintptr_t)a.splitk_ws & 15) == 0))
+            return form(use8 ? wide : (wide == W5 ? T256x320 : T256x256), sk);
     }
-    for (int i = 0; i < G; ++i) grp.a[i] = grp_at(a, i);
-    prof_igemm(a, "");
-    sym();
-    LAUNCH(tag, (igemm8_kernel<NI, MODE>), dim3(per * G), dim3(512), smem, s, grp, per, ntm, ntn, 1, order, (long)-1);
+    const char* const forced = policy_raw(P_IGEMM_FORCE);
+    if (const char* f = forced) {      // tile experiments (tools/tile_experiment.py), row outputs only
+        auto named = [&](int t) { return kTiles[t].force && !strcmp(f, kTiles[t].force); };
+        if (swap && rows && a.nseg == 1 && !a.geglu) {
+            // round 5, short launches of the small-M chain (tools/gemm_order_bench small): 4-wave tiles at three workgroups per CU
+            for (int t : {T128x128x32, T128x64x64, T64x64x64, T128x128x64})
+                if (named(t) && (kTiles[t].bk == 32 || bk64)) return form(t);
+            if (!strcmp(f, "wide") && use8 && a.Nout % kTiles[wide].bn == 0) return form(wide);
+        }
+        // (a mixed-layout problem -- Q | K row-major + V^T transposed -- only takes a forced tile whose width divides the transposed
+        // segment's first column: a tile must lie in one segment, the epilogue's choice is workgroup-uniform; ADVICE r5)
+        if (swap && rows)
+            for (int t : {T128x256, T256x128, T4w256x128, T4w128x256})
+                if (named(t) && al(kTiles[t].bn)) return form(t);
+    }
+    // Epilogue-heavy token GEMMs at large M with a SHORT k-loop (measured, tools/tile_experiment.py -> profiles/r02_tile_experiment.log,
+    // re-measured against the 8-phase kernel in round 4, profiles/r04_step_old_vs_8phase.txt): two resident workgroups per CU let
+    // one's epilogue -- the GEGLU math, or the HBM-bound fp32 residual read + fp32 master + fp16 mirror write of a stream update --
+    // run under the other's k-loop, which the one-workgroup-per-CU wide tile cannot.  GEGLU 512 -> 4096 at M = 131072: 653 (256x128
+    // pair) vs 635 TFLOP/s (8-phase); stream update K = 320: 273 vs 221.  From K = 2048 on the 8-phase loop wins (815 vs 740).
+    const bool force8 = igemm8_mode() == 2;
+    if (!force8 && rows && a.M >= 65536 && swap && a.nseg == 1 && a.seg[0].fmt == SEG_ROW && a.Nout % 256 == 0 && al(256)) {
+        const bool f32_stream = a.seg[0].dtype == DT_F32 || (a.res && a.res_f32);      // fp32 rows written and / or read per element
+        if (a.geglu) return form(T256x128);
+        if (f32_stream && a.Ktot <= 1024) return form(T128x256);
+        // fp16 stream updates (the adapter's token stream since round 4) with a k-loop of <= 8 k-tiles: the residual read + store of
+        // the epilogue still outweighs the loop -- M131072 N512 K320 + residual: 0.164 ms (8-phase) vs 0.128 ms (this pair tile),
+        // -0.12 ms per SDXL step, -0.27 ms fused (one call, gpurun_out/r4p); CTRL_SHORTK_PAIR=0 switches it off
+        const bool pair16 = !policy_is0(P_SHORTK_PAIR);
+        if (pair16 && a.res && a.Ktot <= 512) return form(T128x256);
+    }
+    // the 8-phase wide tiles wherever the grid fills the chip with them (1.3-1.5x the BK = 32 ring kernel on plain epilogues and
+    // long k-loops: convolutions 543 -> 671 TFLOP/s as a class)
+    if (use8 && forced == nullptr) {
+        if (a.Nout % 320 == 0 && (tiles(256, 320) >= 160 || force8) && !a.geglu && al(320)) return form(W5);
+        if (a.Nout % 256 == 0 && (tiles(256, 256) >= 200 || force8) && al(256)) return form(W4);
+    }
+    // (vector-epilogue variant only: the scalar-epilogue one does not fit the register file at this tile size)
+    if (tiles(256, 256) >= 200 && eff(256) > 0.9 && swap && al(256)) return form(T256x256);
+    // N = 320 / 640 / 960 / 1280 / 1920 / 3840 (every conv and QKV width of the path): 256x320 tile, 128x80 per wave
+    if (a.Nout % 320 == 0 && tiles(256, 320) >= 160 && swap && !a.geglu && al(320)) return form(T256x320);
+    if (!bk64) {
+        if (tiles(128, 128) >= 192 && al(128)) return either(T128x128x32);
+        return either(T64x64x32);
+    }
+    // (a 256x128x64 tile at two workgroups per CU stood here: every instantiation spilled inside its MFMA loop -- 128 registers do
+    // not hold a 64-deep fragment set -- and the shapes it served now run on the 8-phase tiles; removed in round 4)
+    // Short launches of the small-M chains (the ControlNet at b = 8, the 64^2 .. 8^2 adapter levels: a few waves of tiles, k-loops of
+    // 5 .. 40 k-tiles): what counts is how many workgroups a CU can interleave, not the tile's LDS traffic per FLOP.  Measured on the
+    // path's shapes (tools/gemm_order_bench small -> profiles/r05_gemm_small_tiles.txt): the 4-wave 128 x 128 x 32 tile at three
+    // workgroups per CU beats the 8-wave 128 x 128 x 64 tile (one per CU) by 10-18 % from ~500 tiles on, the 64 x 64 x 64 tile
+    // (three per CU) by 10-20 % below that for N <= 1280.  CTRL_SMALL_TILES=0: the round-4 choice.
+    const bool small_tiles = !policy_is0(P_SMALL_TILES);
+    if (small_tiles && rows && swap && !a.geglu) {
+        if (tiles(128, 128) >= 512 && eff(128) > 0.8 && al(128)) return form(T128x128x32);
+        if (tiles(128, 128) < 512 && a.Nout <= 1280 && al(64)) return form(T64x64x64);
+    }
+    if (tiles(128, 128) >= 192 && eff(128) > 0.8 && al(128)) return either(T128x128x64);
+    if (tiles(128, 64) >= 192) return either(T128x64x64);
+    return either(T64x64x64);
+}
+
+// what a launch of the form records: the kernel symbol as rocprofv3 prints it, and the split-K part of its prof_detail
+void form_symbol(const IGemmForm& f, int mode, char* buf, size_t cap) {
+    const Tile& T = kTiles[f.tile];
+    if (T.ni) snprintf(buf, cap, "igemm8_kernel<%d, %d>", T.ni, mode);
+    else snprintf(buf, cap, "igemm_kernel<%d, %d, %d, %d, %d, %d, %d, %s>", T.bm, T.bn, T.bk, T.wm, T.wn, T.nstage, mode, T.swap ? "true" : "false");
+}
+void form_splitk_note(const IGemmForm& f, char* buf, size_t cap) {
+    if (f.splitk > 1) snprintf(buf, cap, " splitk%d%s", f.splitk, f.reduce == RED_INLAUNCH ? " in-launch" : "");
+    else buf[0] = 0;
+}
+
+// ---- the launcher ----
+// split-K in the finish-kernel form: the GEMM writes fp32 row slabs, every epilogue term is applied once by the finish kernel
+inline IGemmArgs splitk_slab_desc(const IGemmArgs& a) {
+    IGemmArgs p = a;
+    p.bias = nullptr; p.rowvec = nullptr; p.res = nullptr; p.res_f32 = 0; p.act = 0; p.scale = 1.f; p.out16 = nullptr;
+    p.blend_mix = nullptr; p.blend_x = nullptr;
+    p.nseg = 1;
+    p.seg[0] = IGemmSeg{a.splitk_ws, a.Nout, 0, a.Nout, SEG_ROW, DT_F32, 1, 0};
+    return p;
+}
+int launch_splitk_finish(const IGemmArgs* probs, int n, int splitk, hipStream_t s) {
+    for (int i = 0; i < n; ++i) {
+        const IGemmArgs& ai = probs[i];
+        const size_t total = (size_t)ai.M * (ai.Nout / 8);
+        size_t blocks = (total + 255) / 256;
+        if (blocks > 4096) blocks = 4096;
+        PROF_WORK(0, 4.0 * splitk * ai.M * ai.Nout);
+        prof_detail("M%d N%d splitk%d", ai.M, ai.Nout, splitk);
+        LAUNCH("splitk_finish", splitk_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, s, ai, (const float*)ai.splitk_ws, splitk);
+    }
     return 0;
+}
+void prof_igemm(const IGemmForm& f, const IGemmArgs& a, int G) {
+    if (!g_prof_on) return;
+    // algorithmic work = the reference op's: a split operand doubles the K the kernel walks, not the FLOPs that count
+    const double kalg = a.a_split ? 0.5 * a.Ktot : (double)a.Ktot;
+    PROF_WORK(G * 2.0 * a.M * a.Nout * kalg, G * 2.0 * ((double)a.M * a.Cin + (double)a.Nout * a.Ktot + (double)a.M * a.Nout));
+    char grp[16] = "", extra[40], sym[96];
+    if (G > 1) snprintf(grp, sizeof(grp), " x%d", G);
+    form_splitk_note(f, extra, sizeof(extra));
+    prof_detail("M%d N%d K%d taps%d%s%s%s%s", a.M, a.Nout, a.Ktot, a.taps, a.a_split ? " split-A" : "", a.geglu ? " geglu" : "", extra, grp);
+    form_symbol(f, a.mode, sym, sizeof(sym));
+    prof_symbol("%s", sym);
+}
+
+// One launch of `n` same-form problems (igemm_same_form; a plain launch is a group of one) in the form the selector chose for probs[0]
+int launch(const IGemmForm& f, const IGemmArgs* probs, int n, hipStream_t s) {
+    const IGemmArgs& a = probs[0];
+    const Tile& T = kTiles[f.tile];
+    const void* const kern = T.kern[a.mode];
+    static bool attr_done[kNumTiles][3][kMaxDevices] = {};       // function attributes are per device
+    bool& done = attr_done[f.tile][a.mode][cur_device()];
+    if (!done) {
+        HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)T.smem));
+        done = true;
+    }
+    const half_t* zeros = nullptr;
+    if (!T.ni) {
+        zeros = zero_page();
+        CTRL_CHECK(zeros != nullptr, "igemm: could not allocate the zero page");
+    }
+    int ntm = (a.M + T.bm - 1) / T.bm, ntn = (a.Nout + T.bn - 1) / T.bn, splitk = f.splitk, order = f.order;
+    // workgroups per problem: a group pads them to a multiple of 8 (XCD of a workgroup = its local index % 8, tile_order.h)
+    int per = ntm * ntn * splitk;
+    if (n > 1) per = (per + 7) & ~7;
+    long red_off = -1;
+    IGemmGroup grp;
+    for (int i = 0; i < n; ++i) grp.a[i] = f.reduce == RED_FINISH ? splitk_slab_desc(probs[i]) : probs[i];
+    if (f.reduce == RED_INLAUNCH) {
+        // ticket words: the caller's zeroed ones, or the tail of the scratch, zeroed here (a kernel node: see op_fill_zero)
+        red_off = f.own_tickets ? -2L : (long)align256(splitk_frag_bytes(a, splitk));
+        for (int i = 0; i < n && !f.own_tickets; ++i) TRY(op_fill_zero((char*)probs[i].splitk_ws + red_off, splitk_twords(a, splitk) * sizeof(int), s));
+    }
+    prof_igemm(f, a, n);
+    void* ring_args[] = {&grp, &per, &ntm, &ntn, &zeros, &splitk, &order};
+    void* wide_args[] = {&grp, &per, &ntm, &ntn, &splitk, &order, &red_off};
+    const char* tag = a.mode == IG_ROWS ? "igemm_rows" : (a.mode == IG_CONV2D ? "igemm_conv" : "igemm_temporal");
+    if (g_prof_on) prof_before(tag, "igemm", (long)per * n * T.threads, s);
+    (void)hipLaunchKernel(kern, dim3(per * n), dim3(T.threads), T.ni ? wide_args : ring_args, T.smem, s);
+    if (g_prof_on) prof_after(s);
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) CTRL_FAIL(std::string("launch ") + tag + ": " + hipGetErrorString(le));
+    return f.reduce == RED_FINISH ? launch_splitk_finish(probs, n, splitk, s) : 0;
 }
 
 }  // namespace
-
-// number of K splits op_igemm will use for this problem (1 = none); callers size splitk_ws = factor*M*Nout*4 bytes
 
 int igemm_set_wide(int mode) {
     if (mode < -1 || mode > 2) return 1;
@@ -1102,160 +1263,27 @@ void igemm_tile_of(int bid, int ntm, int ntn, int mode, int group, int* tile_m, 
     tileorder::tile_of(bid, ntm, ntn, tileorder::make_order(mode, group), tile_m, tile_n);
 }
 
+// number of K splits op_igemm will use for this problem given scratch (1 = none)
+int igemm_splitk_factor(const IGemmArgs& a) { return splitk_factor(a, can_use8(a, can_swap(a))); }
+
 // bytes of split-K scratch that let op_igemm use its best form for `sk` splits: the row slabs of the finish-kernel form, or (wide
 // tiles, 2..4 splits) the tile-shaped fragment slabs + ticket words of the in-launch reduction, whichever is larger
 size_t igemm_splitk_ws_bytes(const IGemmArgs& a, int sk) {
-    const size_t rows = (size_t)sk * a.M * a.Nout * sizeof(float);
-    const int bn = (a.Nout % 320 == 0) ? 320 : 256;
-    const size_t tiles = (size_t)((a.M + 255) / 256) * ((a.Nout + bn - 1) / bn);
-    // (fragment slabs + ticket words for callers that do not hand in their own: one word per tile for 2..4 splits, five for the
-    //  two-level reduction of 5..16 splits)
-    const size_t frag = (tiles * sk * 256 * bn * sizeof(float) + 255) / 256 * 256 + tiles * (sk > 4 ? 5 : 1) * sizeof(int);
+    const size_t rows = splitk_rows_bytes(a, sk), frag = align256(splitk_frag_bytes(a, sk)) + splitk_twords(a, sk) * sizeof(int);
     return rows > frag ? rows : frag;
 }
 
 // ticket words (one per 256-row output tile) of the in-launch reduction for `sk` splits; 0 when that form does not apply
-size_t igemm_splitk_ticket_words(const IGemmArgs& a, int sk) {
-    if (sk < 2 || sk > 16) return 0;
-    const int bn = (a.Nout % 320 == 0) ? 320 : 256;
-    return (size_t)((a.M + 255) / 256) * ((a.Nout + bn - 1) / bn) * (sk > 4 ? 5 : 1);
-}
-
-int igemm_splitk_factor(const IGemmArgs& a) {
-    if (a.geglu || a.nseg != 1 || a.seg[0].fmt != SEG_ROW || a.Nout % 64 != 0 || a.Cin % 32 != 0 || a.mode == IG_TEMPORAL) return 1;
-    const int bn = (a.Nout % 320 == 0) ? 320 : 256;
-    if (a.Nout % bn != 0) return 1;
-    const long tiles = (long)((a.M + 255) / 256) * (a.Nout / bn);
-    const int nk32 = a.Ktot / 32;
-    if (tiles >= 160 || nk32 < 64) return 1;
-    int sk = (int)((256 + tiles - 1) / tiles);
-    if (sk > 16) sk = 16;
-    while (sk > 1 && nk32 / sk < 16) --sk;
-    // The kernels give split s the k-tiles [s * per, (s + 1) * per) with per = ceil(nk / sk) -- rounded up to even for the paired
-    // split-operand walk, which never cuts a (hi, lo) pair -- in THEIR k-tile depth: 64 for the 8-phase kernel, 32 for the ring kernel.
-    // Pick sk such that the last split still has work in the depth of the kernel that will run (ADVICE r2 / r4: 640 -> 640 3x3 at 24
-    // tiles: nk64 = 90, sk = 11, per = 9 left split 10 empty -- an idle workgroup whose prologue DMA started at k = Ktot)
-    const int depth = can_use8(a) ? 64 : 32;
-    const int nk = a.Ktot / depth;
-    auto per_of = [&](int f) { int p = (nk + f - 1) / f; if (a.a_split == 2) p = (p + 1) & ~1; return p; };
-    while (sk > 1 && (long)(sk - 1) * per_of(sk) >= nk) --sk;
-    return sk;
-}
-namespace {
-
-template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int NSTAGE, int MODE>
-int launch_cfg(const IGemmArgs& a, hipStream_t s) {
-    if (can_swap(a)) return launch_cfg2<BM, BN, BK, WAVES_M, WAVES_N, NSTAGE, MODE, true>(a, s);
-    return launch_cfg2<BM, BN, BK, WAVES_M, WAVES_N, NSTAGE, MODE, false>(a, s);
-}
-
-// first column of the transposed last segment of a MIXED segment list on the vector epilogue (0 = not such a problem): every tile must
-// lie in one segment, so only tile widths that divide it may be chosen
-int mixed_boundary(const IGemmArgs& a) {
-    if (a.nseg < 2 || a.seg[a.nseg - 1].fmt != SEG_TRANSPOSED || !can_swap(a)) return 0;
-    return a.seg[a.nseg - 1].col_begin;
-}
-
-template <int MODE>
-int dispatch(const IGemmArgs& a, hipStream_t s) {
-    const bool bk64 = (a.Cin % 64) == 0;
-    const int mb = mixed_boundary(a);
-    auto al = [&](int bn) { return mb == 0 || mb % bn == 0; };
-    // Tile choice: 256x128 (8 waves) when the grid still over-fills the 256 CUs, 128x128 otherwise, 64x64 for small
-    // problems.  N extents that are not multiples of 128 pay padded columns, so the waste is weighed against tile size.
-    // (a grouped launch fills the chip with all its problems: the tile is sized for the group, unless the caller wants every problem
-    // computed with the tile it would get alone -- ctrl_group_launches(2), bit-identical to one-by-one launches)
-    const long gmul = group_tiles_as_alone() ? 1 : grp_count();
-    auto tiles = [&](int bm, int bn) { return gmul * (long)((a.M + bm - 1) / bm) * ((a.Nout + bn - 1) / bn); };
-    auto eff = [&](int bn) { return (double)a.Nout / (double)(((a.Nout + bn - 1) / bn) * bn); };
-    // 256x256 (8 waves, 128x64 per wave): fewest LDS bytes per FLOP -- the limiter of the smaller tiles on this chip
-    // split-K: small-M / long-K problems (the ControlNet's low-resolution 3x3 convs) leave most CUs idle with 256-row
-    // tiles and run far below MFMA speed with small tiles; splitting the reduction fills the chip with the wide tile
-    {
-        const int sk = (a.splitk_ws && can_swap(a)) ? igemm_splitk_factor(a) : 1;
-        if (sk > 1 && (size_t)a.splitk_ws_bytes >= (size_t)sk * a.M * a.Nout * sizeof(float) && (((uintptr_t)a.splitk_ws & 15) == 0)) {
-            if (can_use8(a) && a.Nout % 320 == 0) return launch8<5, MODE>(a, s, sk);
-            if (can_use8(a) && a.Nout % 256 == 0) return launch8<4, MODE>(a, s, sk);
-            if (a.Nout % 320 == 0) return launch_cfg2<256, 320, 32, 2, 4, 4, MODE, true>(a, s, sk);
-            return launch_cfg2<256, 256, 32, 2, 4, 4, MODE, true>(a, s, sk);
-        }
-    }
-    const char* const forced = policy_raw(P_IGEMM_FORCE);
-    if (const char* f = forced) {      // tile experiments (tools/tile_experiment.py), row outputs only
-        if (can_swap(a) && MODE == IG_ROWS && a.nseg == 1 && !a.geglu) {
-            // round 5, short launches of the small-M chain (tools/gemm_order_bench small): 4-wave tiles at three workgroups per CU
-            if (!strcmp(f, "128x128x32")) return launch_cfg2<128, 128, 32, 2, 2, 3, MODE, true>(a, s);
-            if (!strcmp(f, "128x64x64") && bk64) return launch_cfg2<128, 64, 64, 2, 2, 3, MODE, true>(a, s);
-            if (!strcmp(f, "64x64x64") && bk64) return launch_cfg2<64, 64, 64, 2, 2, 3, MODE, true>(a, s);
-            if (!strcmp(f, "128x128x64") && bk64) return launch_cfg2<128, 128, 64, 2, 4, 4, MODE, true>(a, s);
-            if (!strcmp(f, "wide") && can_use8(a)) {
-                if (a.Nout % 320 == 0) return launch8<5, MODE>(a, s);
-                if (a.Nout % 256 == 0) return launch8<4, MODE>(a, s);
-            }
-        }
-        // (a mixed-layout problem -- Q | K row-major + V^T transposed -- only takes a forced tile whose width divides the transposed
-        // segment's first column: a tile must lie in one segment, the epilogue's choice is workgroup-uniform; ADVICE r5)
-        if (can_swap(a) && MODE == IG_ROWS) {
-            if (!strcmp(f, "128x256") && al(256)) return launch_cfg2<128, 256, 32, 2, 4, 3, MODE, true>(a, s);
-            if (!strcmp(f, "256x128") && al(128)) return launch_cfg2<256, 128, 32, 4, 2, 3, MODE, true>(a, s);
-            if (!strcmp(f, "4w256x128") && al(128)) return launch_cfg2<256, 128, 32, 2, 2, 3, MODE, true>(a, s);      // 4 waves x 256 registers, two workgroups per CU
-            if (!strcmp(f, "4w128x256") && al(256)) return launch_cfg2<128, 256, 32, 1, 4, 3, MODE, true>(a, s);
-        }
-    }
-    // Epilogue-heavy token GEMMs at large M with a SHORT k-loop (measured, tools/tile_experiment.py -> profiles/r02_tile_experiment.log,
-    // re-measured against the 8-phase kernel in round 4, profiles/r04_step_old_vs_8phase.txt): two resident workgroups per CU let
-    // one's epilogue -- the GEGLU math, or the HBM-bound fp32 residual read + fp32 master + fp16 mirror write of a stream update --
-    // run under the other's k-loop, which the one-workgroup-per-CU wide tile cannot.  GEGLU 512 -> 4096 at M = 131072: 653 (256x128
-    // pair) vs 635 TFLOP/s (8-phase); stream update K = 320: 273 vs 221.  From K = 2048 on the 8-phase loop wins (815 vs 740).
-    const bool force8 = igemm8_mode() == 2;
-    if (!force8 && MODE == IG_ROWS && a.M >= 65536 && can_swap(a) && a.nseg == 1 && a.seg[0].fmt == SEG_ROW && a.Nout % 256 == 0 && al(256)) {
-        const bool f32_stream = a.seg[0].dtype == DT_F32 || (a.res && a.res_f32);      // fp32 rows written and / or read per element
-        if (a.geglu) return launch_cfg2<256, 128, 32, 4, 2, 3, MODE, true>(a, s);
-        if (f32_stream && a.Ktot <= 1024) return launch_cfg2<128, 256, 32, 2, 4, 3, MODE, true>(a, s);
-        // fp16 stream updates (the adapter's token stream since round 4) with a k-loop of <= 8 k-tiles: the residual read + store of
-        // the epilogue still outweighs the loop -- M131072 N512 K320 + residual: 0.164 ms (8-phase) vs 0.128 ms (this pair tile),
-        // -0.12 ms per SDXL step, -0.27 ms fused (one call, gpurun_out/r4p); CTRL_SHORTK_PAIR=0 switches it off
-        const bool pair16 = !policy_is0(P_SHORTK_PAIR);
-        if (pair16 && a.res && a.Ktot <= 512) return launch_cfg2<128, 256, 32, 2, 4, 3, MODE, true>(a, s);
-    }
-    // the 8-phase wide tiles wherever the grid fills the chip with them (1.3-1.5x the BK = 32 ring kernel on plain epilogues and
-    // long k-loops: convolutions 543 -> 671 TFLOP/s as a class)
-    if (can_use8(a) && forced == nullptr) {
-        if (a.Nout % 320 == 0 && (tiles(256, 320) >= 160 || force8) && !a.geglu && al(320)) return launch8<5, MODE>(a, s);
-        if (a.Nout % 256 == 0 && (tiles(256, 256) >= 200 || force8) && al(256)) return launch8<4, MODE>(a, s);
-    }
-    // (vector-epilogue variant only: the scalar-epilogue one does not fit the register file at this tile size)
-    if (tiles(256, 256) >= 200 && eff(256) > 0.9 && can_swap(a) && al(256)) return launch_cfg2<256, 256, 32, 2, 4, 4, MODE, true>(a, s);
-    // N = 320 / 640 / 960 / 1280 / 1920 / 3840 (every conv and QKV width of the path): 256x320 tile, 128x80 per wave
-    if (a.Nout % 320 == 0 && tiles(256, 320) >= 160 && can_swap(a) && !a.geglu && al(320)) return launch_cfg2<256, 320, 32, 2, 4, 4, MODE, true>(a, s);
-    if (!bk64) {
-        if (tiles(128, 128) >= 192 && al(128)) return launch_cfg<128, 128, 32, 2, 2, 3, MODE>(a, s);
-        return launch_cfg<64, 64, 32, 2, 2, 3, MODE>(a, s);
-    }
-    // (a 256x128x64 tile at two workgroups per CU stood here: every instantiation spilled inside its MFMA loop -- 128 registers do
-    // not hold a 64-deep fragment set -- and the shapes it served now run on the 8-phase tiles; removed in round 4)
-    // Short launches of the small-M chains (the ControlNet at b = 8, the 64^2 .. 8^2 adapter levels: a few waves of tiles, k-loops of
-    // 5 .. 40 k-tiles): what counts is how many workgroups a CU can interleave, not the tile's LDS traffic per FLOP.  Measured on the
-    // path's shapes (tools/gemm_order_bench small -> profiles/r05_gemm_small_tiles.txt): the 4-wave 128 x 128 x 32 tile at three
-    // workgroups per CU beats the 8-wave 128 x 128 x 64 tile (one per CU) by 10-18 % from ~500 tiles on, the 64 x 64 x 64 tile
-    // (three per CU) by 10-20 % below that for N <= 1280.  CTRL_SMALL_TILES=0: the round-4 choice.
-    const bool small_tiles = !policy_is0(P_SMALL_TILES);
-    if (small_tiles && MODE == IG_ROWS && can_swap(a) && !a.geglu) {
-        if (tiles(128, 128) >= 512 && eff(128) > 0.8 && al(128)) return launch_cfg2<128, 128, 32, 2, 2, 3, MODE, true>(a, s);
-        if (tiles(128, 128) < 512 && a.Nout <= 1280 && al(64)) return launch_cfg2<64, 64, 64, 2, 2, 3, MODE, true>(a, s);
-    }
-    if (tiles(128, 128) >= 192 && eff(128) > 0.8 && al(128)) return launch_cfg<128, 128, 64, 2, 4, 4, MODE>(a, s);
-    if (tiles(128, 64) >= 192) return launch_cfg<128, 64, 64, 2, 2, 3, MODE>(a, s);
-    return launch_cfg<64, 64, 64, 2, 2, 3, MODE>(a, s);
-}
-
-}  // namespace
+size_t igemm_splitk_ticket_words(const IGemmArgs& a, int sk) { return (sk < 2 || sk > 16) ? 0 : splitk_twords(a, sk); }
 
 static int igemm_validate(const IGemmArgs& a);
-static int igemm_dispatch(const IGemmArgs& a, hipStream_t s) {
-    if (a.mode == IG_CONV2D) return dispatch<IG_CONV2D>(a, s);
-    if (a.mode == IG_TEMPORAL) return dispatch<IG_TEMPORAL>(a, s);
-    return dispatch<IG_ROWS>(a, s);
+// range check (debug aid: every fp16 value the epilogue writes is tested for inf / nan) and validation of a descriptor about to be launched
+static int igemm_prepare(IGemmArgs& b) {
+    if (!b.nonfinite && range_check_on()) {
+        b.nonfinite = range_flag();
+        CTRL_CHECK(b.nonfinite != nullptr, "igemm: the range check is on but its flag word could not be allocated");
+    }
+    return igemm_validate(b);
 }
 int op_igemm(const IGemmArgs& a, hipStream_t s) {
     if (t_collect) {                                 // lock-step replay of sibling blocks: deposited, launched by the collector's flush()
@@ -1266,27 +1294,32 @@ int op_igemm(const IGemmArgs& a, hipStream_t s) {
         return 0;
     }
     IGemmArgs b = a;
-    if (!b.nonfinite && range_check_on()) {          // debug aid: every fp16 value the epilogue writes is tested for inf / nan
-        b.nonfinite = range_flag();
-        CTRL_CHECK(b.nonfinite != nullptr, "igemm: the range check is on but its flag word could not be allocated");
-    }
-    TRY(igemm_validate(b));
-    return igemm_dispatch(b, s);
+    TRY(igemm_prepare(b));
+    return launch(igemm_select(b, 1), &b, 1, s);
 }
 
-// One fixed form for the text encoder (plan_text.cpp): the 64 x 64 x 64 tile at every M, never split-K, never grouped -- every output row
-// is then computed by the same instruction sequence whatever the batch, so a prompt encodes to the same bits alone or inside a batch
-// (dispatch() sizes the tile by M).  Row-major problems with Cin % 64 == 0 and the aligned vector epilogue only.
+// the pinned form of the encoder plans (igemm_select: pinned)
 int op_igemm_pinned(const IGemmArgs& a, hipStream_t s) {
     IGemmArgs b = a;
     b.splitk_ws = nullptr; b.splitk_ws_bytes = 0; b.splitk_tickets = nullptr;
-    if (!b.nonfinite && range_check_on()) {
-        b.nonfinite = range_flag();
-        CTRL_CHECK(b.nonfinite != nullptr, "igemm: the range check is on but its flag word could not be allocated");
-    }
-    TRY(igemm_validate(b));
-    CTRL_CHECK(b.mode == IG_ROWS && b.Cin % 64 == 0 && !b.geglu && can_swap(b), "igemm_pinned: needs an aligned row-major problem with Cin % 64 == 0");
-    return launch_cfg2<64, 64, 64, 2, 2, 3, IG_ROWS, true>(b, s);
+    TRY(igemm_prepare(b));
+    const IGemmForm f = igemm_select(b, 1, true);
+    CTRL_CHECK(f.tile >= 0, "igemm_pinned: needs an aligned row-major problem with Cin % 64 == 0");
+    return launch(f, &b, 1, s);
+}
+
+// Test ABI (ctrl_igemm_select): what a launch of `a` as one of `group_n` problems would record -- the kernel symbol, " splitkN" for a
+// split problem and " in-launch" where that reduction is taken -- without launching anything
+int igemm_select_text(const IGemmArgs& a, int group_n, bool pinned, char* buf, int cap) {
+    CTRL_CHECK(buf && cap > 0 && group_n >= 1 && group_n <= kMaxIGemmGroup, "igemm_select: bad arguments");
+    TRY(igemm_validate(a));
+    const IGemmForm f = igemm_select(a, group_n, pinned);
+    CTRL_CHECK(f.tile >= 0, "igemm_pinned: needs an aligned row-major problem with Cin % 64 == 0");
+    char sym[96], note[40];
+    form_symbol(f, a.mode, sym, sizeof(sym));
+    form_splitk_note(f, note, sizeof(note));
+    snprintf(buf, (size_t)cap, "%s%s", sym, note);
+    return 0;
 }
 
 // what has to agree for two problems to share a launch: every field the dispatcher, the launch geometry and the kernels' uniform
@@ -1321,16 +1354,9 @@ int op_igemm_group(const IGemmArgs* a, int n, hipStream_t s) {
     IGemmArgs b[kMaxIGemmGroup];
     for (int i = 0; i < n; ++i) {
         b[i] = a[i];
-        if (!b[i].nonfinite && range_check_on()) {
-            b[i].nonfinite = range_flag();
-            CTRL_CHECK(b[i].nonfinite != nullptr, "igemm: the range check is on but its flag word could not be allocated");
-        }
-        TRY(igemm_validate(b[i]));
+        TRY(igemm_prepare(b[i]));
     }
-    t_grp = b; t_grp_n = n;            // the launch functions pick the siblings up from here
-    const int rc = igemm_dispatch(b[0], s);
-    t_grp = nullptr; t_grp_n = 1;
-    return rc;
+    return launch(igemm_select(b[0], n), b, n, s);
 }
 
 static int igemm_validate(const IGemmArgs& a) {

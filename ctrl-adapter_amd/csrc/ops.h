@@ -28,6 +28,9 @@ int igemm_set_order(const char* spec);
 // eligible problem (the parity tests run their small shapes through it this way), -1 back to CTRL_IGEMM8 / the default; 0 = accepted
 int igemm_set_wide(int mode);
 void igemm_tile_of(int bid, int ntm, int ntn, int mode, int group, int* tile_m, int* tile_n);
+// what op_igemm (pinned: op_igemm_pinned) would record for `a` as one of group_n same-form problems of a launch: the kernel symbol, then
+// " splitkN" for a split problem and " in-launch" where that reduction is taken; launches nothing, needs no device (ctrl_igemm_select)
+int igemm_select_text(const IGemmArgs& a, int group_n, bool pinned, char* buf, int cap);
 // Grouped launch (round 5): n <= kMaxIGemmGroup problems of the same shape and epilogue form (sibling adapter blocks of one
 // pyramid level) in ONE launch -- every problem computed exactly as it would be alone; problems that do not agree are launched one
 // by one.  See igemm.hip: IGemmGroup.

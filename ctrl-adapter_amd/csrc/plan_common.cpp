@@ -83,6 +83,23 @@ int run_layernorm(Ctx& cx, const Norm& n, const TV& x, half_t* y, int M, int dim
     return 0;
 }
 
+// a GEMM with the split-K scratch and tickets the selector asks for, carved from the stack
+static int run_gemm(Ctx& cx, IGemmArgs g) {
+    const size_t mk = cx.mark();
+    const int sk = igemm_splitk_factor(g);
+    if (sk > 1) {
+        g.splitk_ws_bytes = (int64_t)igemm_splitk_ws_bytes(g, sk);
+        g.splitk_ws = cx.alloc((size_t)g.splitk_ws_bytes);
+        // ticket words of the in-launch reduction: a slice of the pool the forward zeroes ONCE (with the GroupNorm tickets) instead
+        // of a fill launch in front of every split-K convolution
+        const size_t tw = igemm_splitk_ticket_words(g, sk);
+        if (tw) g.splitk_tickets = (int32_t*)cx.stats(tw);
+    }
+    RUN(cx, op_igemm(g, cx.s));
+    cx.release(mk);
+    return 0;
+}
+
 int run_conv(Ctx& cx, const ConvW& c, const half_t* x, const TV& y, int N, int Hin, int Win, const ConvOpts& o) {
     const int k = c.taps == 9 ? 3 : 1, pads = c.taps == 9 ? (o.tap_origin ? 1 : 2) : 0;     // padding summed over both sides
     const int Hout = (Hin * o.up + pads - k) / o.stride + 1, Wout = (Win * o.up + pads - k) / o.stride + 1;
@@ -98,19 +115,7 @@ int run_conv(Ctx& cx, const ConvW& c, const half_t* x, const TV& y, int N, int H
     set_res(g, o.res, c.Cout);
     g.res_up = o.res_up;
     set_out(g, y, c.Cout, c.Cout);
-    const size_t mk = cx.mark();
-    const int sk = igemm_splitk_factor(g);
-    if (sk > 1) {
-        g.splitk_ws_bytes = (int64_t)igemm_splitk_ws_bytes(g, sk);
-        g.splitk_ws = cx.alloc((size_t)g.splitk_ws_bytes);
-        // ticket words of the in-launch reduction: a slice of the pool the forward zeroes ONCE (with the GroupNorm tickets) instead
-        // of a fill launch in front of every split-K convolution
-        const size_t tw = igemm_splitk_ticket_words(g, sk);
-        if (tw) g.splitk_tickets = (int32_t*)cx.stats(tw);
-    }
-    RUN(cx, op_igemm(g, cx.s));
-    cx.release(mk);
-    return 0;
+    return run_gemm(cx, g);
 }
 
 int run_linear(Ctx& cx, const Lin& l, const half_t* x, long ldx, const TV& y, long ldy, int M, const TV& res, long ldres,
@@ -386,21 +391,6 @@ int run_basic_tb(Ctx& cx, const BasicTBW& w, const TV& X, const TV& out, int B, 
 
 // ------------------------------------------------------------------------------------------ KL-VAE mid-block attention
 static constexpr size_t kAttnCap = 256u << 20;     // bytes of the S (fp32) + P (fp16) chunk of the mid-block attention
-
-// a GEMM with the split-K scratch and tickets the dispatcher asks for (carved from the stack, as run_conv does)
-static int run_gemm(Ctx& cx, IGemmArgs g) {
-    const size_t mk = cx.mark();
-    const int sk = igemm_splitk_factor(g);
-    if (sk > 1) {
-        g.splitk_ws_bytes = (int64_t)igemm_splitk_ws_bytes(g, sk);
-        g.splitk_ws = cx.alloc((size_t)g.splitk_ws_bytes);
-        const size_t tw = igemm_splitk_ticket_words(g, sk);
-        if (tw) g.splitk_tickets = (int32_t*)cx.stats(tw);
-    }
-    RUN(cx, op_igemm(g, cx.s));
-    cx.release(mk);
-    return 0;
-}
 
 static IGemmArgs rows_gemm(const half_t* A, long lda, const half_t* W, int M, int Nout, int K, float scale) {
     IGemmArgs g = {};

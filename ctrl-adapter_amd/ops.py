@@ -74,6 +74,14 @@ def igemm_splitk_plan(d):
     return sk, int(lib.ctrl_igemm_splitk_ws_bytes(C.byref(d), sk)), int(lib.ctrl_igemm_splitk_ticket_words(C.byref(d), sk))
 
 
+def igemm_select(d, group_n=1, pinned=False):
+    """what ctrl_op_igemm (pinned: ctrl_op_igemm_pinned) would record for the descriptor `d` (igemm_desc) as one of group_n problems of
+    a launch: "<kernel symbol>[ splitkN[ in-launch]]".  Launches nothing and needs no GPU."""
+    buf = C.create_string_buffer(160)
+    L.check(L.lib().ctrl_igemm_select(C.byref(d), int(group_n), int(bool(pinned)), buf, len(buf)))
+    return buf.value.decode()
+
+
 def igemm_desc(A, lda, W, M, Nout, Cin, taps=1, mode=IG_ROWS, geom=None, bias=None, rowvec=None, rows_per_img=1,
                res=None, ldres=0, scale=1.0, geglu=False, segs=None, F=0, HW=0, out16=None, ld16=0, splitk_ws=None,
                blend_mix=None, blend_x=None, ld_blend=0, a_split=False, out16_lo_off=0, t_pad=False, scale2=0.0, scale2_from=0,

@@ -130,6 +130,11 @@ int ctrl_op_igemm_pinned(const ctrl_igemm_desc* d, void* stream);
 int ctrl_igemm_splitk_factor(const ctrl_igemm_desc* d);
 int64_t ctrl_igemm_splitk_ws_bytes(const ctrl_igemm_desc* d, int splits);
 int64_t ctrl_igemm_splitk_ticket_words(const ctrl_igemm_desc* d, int splits);
+/* Test ABI.  Which kernel form ctrl_op_igemm (pinned != 0: ctrl_op_igemm_pinned) would launch for the descriptor as one of group_n
+   (1..4) same-form problems of a grouped launch, written to buf (cap bytes) as the launch would record it: the kernel symbol with
+   its template arguments, then " splitkN" for a split problem and " in-launch" where that reduction is taken.  Depends on the
+   descriptor, the policy table, ctrl_igemm_set_wide and ctrl_group_launches only: it launches nothing and needs no device. */
+int ctrl_igemm_select(const ctrl_igemm_desc* d, int group_n, int pinned, char* buf, int cap);
 /* Fused GEGLU feed-forward of a transformer block with dim 512 / hidden 2048 (csrc/ffn.hip; diffusers FeedForward(GEGLU) under
    BasicTransformerBlock / TemporalBasicTransformerBlock, model/adapter_spatial_temporal.py:108-130):
        out = epilogue( ((X W1h^T + b1h) * gelu_erf(X W1g^T + b1g)) W2^T )

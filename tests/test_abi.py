@@ -17,8 +17,10 @@ def test_library_exports_every_declared_symbol():
     for name in sorted(declared):
         assert hasattr(lib, name), "libctrlhip.so does not export %s" % name
     assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
-    # the test ABI of the implicit GEMM: the pinned form and the split-K sizing queries (tests/test_gpu_igemm_forms.py)
-    assert {"ctrl_op_igemm_pinned", "ctrl_igemm_splitk_factor", "ctrl_igemm_splitk_ws_bytes", "ctrl_igemm_splitk_ticket_words"} <= declared
+    # the test ABI of the implicit GEMM: the pinned form, the split-K sizing queries (tests/test_gpu_igemm_forms.py) and the form
+    # selector (tests/test_igemm_select_host.py)
+    assert {"ctrl_op_igemm_pinned", "ctrl_igemm_splitk_factor", "ctrl_igemm_splitk_ws_bytes", "ctrl_igemm_splitk_ticket_words",
+            "ctrl_igemm_select"} <= declared
     assert lib.ctrl_abi_version() == _lib.ABI_VERSION == 7
 
 

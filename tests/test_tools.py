@@ -156,3 +156,30 @@ def test_isa_mix_classifier_and_block_split():
     bodies, meta = m.kernels(asm)
     assert list(bodies) == ["_ZN12_GLOBAL__N_114avgpool_kernelEPKvPvii"] and "v_mfma" in bodies[list(bodies)[0]]
     assert meta["_ZN12_GLOBAL__N_114avgpool_kernelEPKvPvii"]["vgpr_count"] == 12
+
+
+def _synthetic_device_asm(kernels, cuid):
+    """a device assembly file in the shape hipcc leaves behind: kernels = [(symbol, instruction)] in emission order"""
+    out = ["\t.amdgcn_target \"amdgcn-amd-amdhsa--gfx950\"\n"]
+    for i, (sym, ins) in enumerate(kernels):
+        out.append("\t.section\t.text.%s,\"axG\",@progbits,%s,comdat\n\t.globl\t%s\n%s:\n\t%s\n.LBB%d_1:%s; in Loop: Header=BB%d_1\n"
+                   "\ts_cbranch_scc1 .LBB%d_1\n.Lfunc_end%d:\n\t.amdhsa_kernel %s\n" % (sym, sym, sym, sym, ins, i, " " * (3 + i), i, i, i, sym))
+    out.append("\t.section\t.AMDGPU.gpr_maximums,\"\",@progbits\n__hip_cuid_%s:\n\t.amdgpu_metadata\n---\namdhsa.kernels:\n" % cuid)
+    for sym, _ in kernels:
+        out.append("  - .agpr_count:    0\n    .name:           %s\n    .vgpr_count:     12\n" % sym)
+    out.append("amdhsa.target:   amdgcn-amd-amdhsa--gfx950\n...\n\t.end_amdgpu_metadata\n")
+    return "".join(out)
+
+
+def test_asm_compare_ignores_emission_order_and_sees_an_instruction(tmp_path, capsys):
+    m = _load("igemm_asm_compare")
+    a, b, c = ("k_a", "v_add_f32_e32 v1, v2, v3"), ("k_b", "v_mul_f32_e32 v1, v2, v3"), ("k_b", "v_mul_f32_e32 v1, v2, v4")
+    files = {}
+    for name, ks, cuid in (("parent", [a, b], "11aa"), ("moved", [b, a], "22bb"), ("changed", [a, c], "11aa"), ("fewer", [a], "11aa")):
+        files[name] = str(tmp_path / (name + ".s"))
+        with open(files[name], "w") as fh:
+            fh.write(_synthetic_device_asm(ks, cuid))
+    assert m.main(files["parent"], files["parent"]) == 0
+    assert m.main(files["parent"], files["moved"]) == 0 and "same order: False" in capsys.readouterr().out
+    assert m.main(files["parent"], files["changed"]) == 1 and "DIFFERS: k_b" in capsys.readouterr().out
+    assert m.main(files["parent"], files["fewer"]) == 1

@@ -6,7 +6,8 @@ trees and diff the output.  Every line must be identical.
            through the mirror that registers them); the text towers' from text_encoder_spec.
   default  (GPU) builds each stand-alone plan (text, vision, VAE encoder, VAE decoder, whole VAE) from seeded weights at the smallest
            shapes that reach every shared code path and prints the sha256 of every output tensor's bytes and of the ordered kernel
-           symbols ops.Profiler records for the call.
+           symbols ops.Profiler records for the call.  The ControlNet and the SDXL adapter follow at 16 x 16 latents, N = 2: the plans
+           whose convolutions split K (scratch and tickets carved per descriptor) and whose sibling blocks share grouped launches.
 
 Only names both trees have are used: the mirrors, synthetic.seeded_init, ops.Profiler and text_encoder._forward_ext (the one entry
 that reaches the text plan's hidden_index)."""
@@ -145,6 +146,21 @@ def gpu_mode():
         dist = vae.encode(x).latent_dist
         return [dist.mean, dist.logvar, vae.decode(dist.mode()).sample]
     case("AutoencoderKL (32,64) encode -> mode -> decode", round_trip)
+
+    # ---- ControlNet (SD-1.5 defaults, cross-attention 768) and the SDXL adapter over its pyramid: 16 x 16 latents, N = 2
+    cn = seeded_init(P.ControlNetModel(cross_attention_dim=768), seed=11).to(dev)
+    ad = seeded_init(P.ControlNetAdapter(**ADAPTER_SDXL), seed=22).to(dev)
+    sample, cond = seeded_tensor((2, 4, 16, 16), 101).half().to(dev), seeded_tensor((2, 3, 128, 128), 103, kind="uniform").half().to(dev)
+    ehs, ehs_a = seeded_tensor((2, 77, 768), 102).half().to(dev), seeded_tensor((2, 77, 2048), 7).half().to(dev)
+    t = torch.tensor([999.0, 249.0]).to(dev)
+
+    def controlnet():
+        down, mid = cn(sample, t, ehs, cond, return_dict=False)
+        return list(down) + [mid]
+    case("controlnet 16x16 N=2", controlnet)
+    down = controlnet()[:-1]
+    case("adapter sdxl over the controlnet pyramid", lambda: [o for o in ad(down, num_frames=1, timestep=torch.tensor(499.0),
+                                                                            encoder_hidden_states=ehs_a)[0] if o is not None])
 
 
 if __name__ == "__main__":
