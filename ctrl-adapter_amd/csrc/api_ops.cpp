@@ -42,6 +42,10 @@ int ctrl_op_flash_attn(const ctrl_attn_desc* d, void* stream) {
     CTRL_CHECK(d != nullptr, "flash_attn: null descriptor");
     return op_flash_attn(*d, S(stream));
 }
+int ctrl_op_flash_attn_group(const ctrl_attn_desc* d, int n, void* stream) {
+    CTRL_CHECK(d != nullptr, "flash_attn_group: null descriptor array");
+    return op_flash_attn_group(d, n, S(stream));
+}
 int ctrl_attn_set_variant(int v) {
     CTRL_CHECK(v >= -1 && v <= 14, "attn_set_variant: variant out of range (-1 = default, 0 = round-2 kernel, 1..14 = attention_d64.hip)");
     return attn_set_variant(v);

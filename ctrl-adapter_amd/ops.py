@@ -231,25 +231,49 @@ def conv2d(x_nhwc, w_packed, Cout, taps=9, stride=1, up=1, bias=None, rowvec=Non
     return out
 
 
-def flash_attn(Q, ldq, K, ldk, Vt, Lkpad, B, heads, D, Lq, Lk, scale=None, kvB=0, k_prescaled=False):
-    out = _f16(B * Lq, heads * D)
+def flash_attn_desc(Q, ldq, K, ldk, Vt, Lkpad, B, heads, D, Lq, Lk, out, ldo, scale=None, kvB=0, k_prescaled=False):
+    """the ctrl_attn_desc of one problem.  Q, K, Vt and out may be views into larger buffers: each is addressed from its first element
+    (data_ptr) with the leading dimension given beside it (ldq / ldk / ldo in elements; Vt rows are Lkpad apart)."""
     d = L.AttnDesc()
     d.Q = Q.data_ptr(); d.ldq = ldq; d.K = K.data_ptr(); d.ldk = ldk; d.Vt = Vt.data_ptr(); d.Lkpad = Lkpad
-    d.O = out.data_ptr(); d.ldo = heads * D
+    d.O = out.data_ptr(); d.ldo = ldo
     d.B = B; d.heads = heads; d.D = D; d.Lq = Lq; d.Lk = Lk; d.kvB = kvB if kvB else B
     d.scale = scale if scale is not None else D ** -0.5
     d.k_prescaled = int(k_prescaled)
+    return d
+
+
+def flash_attn(Q, ldq, K, ldk, Vt, Lkpad, B, heads, D, Lq, Lk, scale=None, kvB=0, k_prescaled=False, out=None, ldo=None):
+    """-> [B*Lq][heads*D] fp16 (dense), or written into `out` (a view whose rows are `ldo` elements apart; default: its row stride)"""
+    if out is None:
+        out = _f16(B * Lq, heads * D)
+        ldo = heads * D
+    elif ldo is None:
+        ldo = out.stride(0)
+    d = flash_attn_desc(Q, ldq, K, ldk, Vt, Lkpad, B, heads, D, Lq, Lk, out, ldo, scale=scale, kvB=kvB, k_prescaled=k_prescaled)
     L.check(L.lib().ctrl_op_flash_attn(C.byref(d), L.cur_stream()))
     return out
 
 
-def temporal_attn(qkv, Bc, F, HW, heads, kv=None, Fq=0, Fl=0):
+def flash_attn_group(descs):
+    """1..4 problems (flash_attn_desc) through ctrl_op_flash_attn_group: one launch when they agree in shape, strides and pointer
+    phase, else one launch each; the caller keeps the tensors behind the descriptors alive"""
+    arr = (L.AttnDesc * len(descs))(*descs)
+    L.check(L.lib().ctrl_op_flash_attn_group(arr, len(descs), L.cur_stream()))
+
+
+def temporal_attn(qkv, Bc, F, HW, heads, kv=None, Fq=0, Fl=0, out=None, ldo=None):
     """qkv [(b f) p][3C] (q | k | v) -> [(b f) p][C]; sharded form: qkv holds the LOCAL Fq query frames as [..][C] rows
-    and kv = the gathered K|V rows [world][Bc][Fl][HW][2C]"""
+    and kv = the gathered K|V rows [world][Bc][Fl][HW][2C].  qkv may be a view (its row stride is the leading dimension); `out`:
+    a view to write into, rows `ldo` elements apart (default: its row stride)"""
     Cc = heads * 64
-    out = _f16(qkv.shape[0], Cc)
+    if out is None:
+        out = _f16(qkv.shape[0], Cc)
+        ldo = Cc
+    elif ldo is None:
+        ldo = out.stride(0)
     d = L.TAttnDesc()
-    d.Q = qkv.data_ptr(); d.ld = qkv.shape[1]; d.O = out.data_ptr(); d.ldo = Cc
+    d.Q = qkv.data_ptr(); d.ld = qkv.stride(0); d.O = out.data_ptr(); d.ldo = ldo
     d.Bc = Bc; d.F = F; d.HW = HW; d.heads = heads; d.scale = 64 ** -0.5
     d.Fq = Fq; d.Fl = Fl
     if kv is not None:

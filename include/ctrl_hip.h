@@ -201,6 +201,10 @@ typedef struct ctrl_attn_desc {
     int32_t pad0_;
 } ctrl_attn_desc;
 int ctrl_op_flash_attn(const ctrl_attn_desc* d, void* stream);
+/* d[0..n), 1 <= n <= 4: the attentions of sibling adapter blocks.  Problems that agree in every shape, stride, scale and in the 16-byte
+   phase of their pointers share ONE launch (workgroup b works on problem b / workgroups-per-problem; with CTRL_GROUP=0, or when
+   the members disagree, n launches in order); the result of every member is bit for bit what ctrl_op_flash_attn gives it alone. */
+int ctrl_op_flash_attn_group(const ctrl_attn_desc* d, int n, void* stream);
 /* Instruction-selection variant of the head_dim-64 long-sequence kernel (csrc/attention_d64.hip): 0 = the round-2 kernel,
    > 0 = the round-3 family (what each number selects is listed in that file); performance only, every variant computes the
    same function.  -1 = back to the default (CTRL_ATTN_VARIANT or the best measured).  Used by tools/attn_bench.cpp. */

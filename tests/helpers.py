@@ -148,3 +148,83 @@ class Guarded:
             raise AssertionError("%s: %d element(s) outside the problem were written; first at buffer index %s (valid region %s of %s)" % (
                 what, int(diff.sum()), tuple(int(v) for v in idx[0]), [(s.start, s.stop) for s in self.valid], tuple(self.buf.shape)))
 
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Element-wise check of an attention result (tests/test_gpu_attn_forms.py; self-test: tests/test_attn_check_host.py)
+#
+#   out[i][d] = sum_j p_ij v_jd / sum_j p_ij,   p_ij = 2^(s_ij - m_i),   s_ij = c * q_i . k_j   (c takes q.k to the exp2 domain;
+#   c = 1 when K arrives pre-scaled), compared with an fp64 reference over the SAME fp16 operands.  With w = softmax weights,
+#   mag = w . |V|, A_ij = |c| * |q_i| . |k_j| and l_i = sum_j 2^(s_ij - max_j s_ij) >= 1, every kernel of the family obeys
+#
+#   |out - ref| <=   [score accumulation]  (W_g . |V| + |ref| * rowsum(W_g)) / (1 - rowsum(W_g)),   W_g = w * (2^delta - 1 + 2^-22),
+#                                          delta_ij = (D + 8) * 2^-24 * (A_ij + max_j A_ij)
+#                  + [P rounded to fp16]   sum_j max(2^-11 * w_ij, 2^-25 / l_i) * |v_jd|            (flash kernels only)
+#                  + [fp32 sums of O, l]   2 * (Lk + ceil(Lk / 64) + 8) * 2^-24 * mag
+#                  + [fp16 output]         2^-11 * |ref| + 2^-25
+#
+# score accumulation: s is a length-D fp32 sum in ANY order whose accumulator also carries the reference point m (the folded
+#   kernels start the MFMA at -m; the plain ones subtract m in one fma), and m is itself one of the row's scores, so every partial sum is
+#   at most A_ij + max_j A_ij in magnitude: (D + 1) roundings, + 7 for c (a rounded fp32 product of two rounded constants) and for the
+#   subtraction of the moved reference point.  A score off by delta multiplies p by 2^delta in the numerator AND the denominator: the
+#   quotient rule gives the expression above (exact, not first order).  2^-22: v_exp_f32 is good to 1 ulp = 2^-23, taken twice (p, and
+#   the rescale factor of a moved reference point).
+# P rounded to fp16: only the numerator sees it (l sums the fp32 values): one round-to-nearest of a p that lies anywhere between the
+#   smallest subnormal and 2^8 (the deferred reference point), i.e. 2^-11 relative or 2^-25 absolute.  The absolute part is taken
+#   against l at the TRUE maximum, where it is largest (a deferred reference point is lower, which scales p up and the error down).
+# fp32 sums: O and l each are a length-Lk sum in any order, rescaled at most once per 64-key tile (one rounding each); + 8: the
+#   exchange of the half-rows' sums, the reciprocal (1 ulp) and the final product.  |ref| <= mag turns the l part into mag as well.
+# fp16 output: one round-to-nearest of the result (2^-25: half the smallest fp16 subnormal).
+# Nothing in it is measured; there is no slack factor.
+# ---------------------------------------------------------------------------------------------------------------------
+ATTN_REL_INF_TOL = 2e-3           # the suite's per-tensor tolerance (tests/test_gpu_ops.py), asserted beside the bound
+
+
+def attn_reference(q, k, v, c, D=None, p_fp16=True):
+    """fp64 reference and element-wise bound of softmax_2(c * q k^T) v.  q [N][Lq][D], k, v [N][Lk][D] (N = batch * heads; k, v may
+    have N = 1: broadcast), c: float.  Returns (ref, bound), both [N][Lq][D] fp64."""
+    q, k, v = q.double(), k.double(), v.double()
+    D = D or q.shape[-1]
+    Lk = k.shape[-2]
+    s = (q @ k.transpose(-1, -2)) * c
+    smax = s.max(-1, keepdim=True).values
+    e = torch.exp2(s - smax)
+    l = e.sum(-1, keepdim=True)
+    w = e / l
+    va = v.abs()
+    ref = w @ v
+    mag = w @ va
+    A = (q.abs() @ k.abs().transpose(-1, -2)) * abs(c)
+    delta = (D + 8) * 2.0 ** -24 * (A + A.max(-1, keepdim=True).values)
+    wg = w * (torch.exp2(delta) - 1 + 2.0 ** -22)
+    sg = wg.sum(-1, keepdim=True)
+    bound = (wg @ va + ref.abs() * sg) / (1 - sg)
+    if p_fp16:
+        bound = bound + torch.maximum(2.0 ** -11 * w, 2.0 ** -25 / l) @ va
+    bound = bound + 2 * (Lk + (Lk + 63) // 64 + 8) * 2.0 ** -24 * mag
+    bound = bound + 2.0 ** -11 * ref.abs() + 2.0 ** -25
+    return ref, bound
+
+
+def assert_attn_close(out, ref, bound, what=""):
+    """every element of `out` finite and within `bound` (attn_reference) of the fp64 `ref`, AND the per-tensor rel_inf within the
+    suite's tolerance.  Returns (worst |err| / bound, rel_inf)."""
+    o = out.detach().cpu().double()
+    assert o.shape == ref.shape, (what, tuple(o.shape), tuple(ref.shape))
+    assert bool(torch.isfinite(o).all()), "%s: %d non-finite outputs (a poisoned pad reached a kept element); first at %s" % (
+        what, int((~torch.isfinite(o)).sum()), tuple(int(v) for v in (~torch.isfinite(o)).nonzero()[0]))
+    err = (o - ref).abs()
+    ratio = err / bound
+    worst = float(ratio.max())
+    rel = float(err.max() / ref.abs().max().clamp_min(1e-12))
+    print("ATTN-CHECK %-78s worst err/bound %.3f  rel_inf %.2e" % (what, worst, rel))
+    bad = err > bound
+    if bool(bad.any()):
+        idx = bad.nonzero()
+        first = tuple(int(v) for v in idx[0])
+        rows = sorted({tuple(int(v) for v in r[:-1]) for r in idx[:4096]})
+        raise AssertionError("%s: %d of %d elements beyond the format-derived bound (worst err/bound %.2f); first at %s: got %.6g want %.6g "
+                             "bound %.3g; rows hit: %s%s" % (what, int(bad.sum()), bad.numel(), worst, first, float(o[first]),
+                                                            float(ref[first]), float(bound[first]), rows[:8], " ..." if len(rows) > 8 else ""))
+    assert rel <= ATTN_REL_INF_TOL, "%s: rel_inf %.3e > %.1e" % (what, rel, ATTN_REL_INF_TOL)
+    return worst, rel

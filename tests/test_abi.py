@@ -21,6 +21,8 @@ def test_library_exports_every_declared_symbol():
     # selector (tests/test_igemm_select_host.py)
     assert {"ctrl_op_igemm_pinned", "ctrl_igemm_splitk_factor", "ctrl_igemm_splitk_ws_bytes", "ctrl_igemm_splitk_ticket_words",
             "ctrl_igemm_select"} <= declared
+    # the grouped attention launch, reached outside a plan only through this entry (tests/test_gpu_attn_forms.py)
+    assert "ctrl_op_flash_attn_group" in declared
     assert lib.ctrl_abi_version() == _lib.ABI_VERSION == 7
 
 
