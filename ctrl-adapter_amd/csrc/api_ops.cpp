@@ -13,6 +13,10 @@ int ctrl_op_igemm_pinned(const ctrl_igemm_desc* d, void* stream) {
     CTRL_CHECK(d != nullptr, "igemm_pinned: null descriptor");
     return op_igemm_pinned(*d, S(stream));
 }
+int ctrl_op_igemm_group(const ctrl_igemm_desc* d, int n, void* stream) {
+    CTRL_CHECK(d != nullptr, "igemm_group: null descriptor array");
+    return op_igemm_group(d, n, S(stream));
+}
 int ctrl_igemm_splitk_factor(const ctrl_igemm_desc* d) { return d ? igemm_splitk_factor(*d) : 0; }
 int64_t ctrl_igemm_splitk_ws_bytes(const ctrl_igemm_desc* d, int splits) { return d ? (int64_t)igemm_splitk_ws_bytes(*d, splits) : 0; }
 int64_t ctrl_igemm_splitk_ticket_words(const ctrl_igemm_desc* d, int splits) { return d ? (int64_t)igemm_splitk_ticket_words(*d, splits) : 0; }
@@ -108,6 +112,10 @@ int ctrl_op_conv3x3_direct(const void* in, int in_dtype, int in_nchw, const floa
 int ctrl_op_conv3x3_small_mfma(const void* x, const void* w, const float* bias, void* out, int N, int Cin, int Cout, int Hin, int Win,
                                int stride, int silu, void* stream) {
     return op_conv3x3_small_mfma((const half_t*)x, (const half_t*)w, bias, H(out), N, Cin, Cout, Hin, Win, stride, silu, S(stream));
+}
+int ctrl_op_pack_conv_w_phase(const void* w, int dtype, void* out, int Cout, int Cin, void* stream) {
+    CTRL_CHECK(w && out && Cout > 0 && Cin > 0, "pack_conv_w_phase: bad arguments");
+    return op_pack_conv_w_phase(w, dtype, H(out), Cout, Cin, S(stream));
 }
 int ctrl_op_pack_conv_w(const void* w, int dtype, void* out, int Cout, int Cin, int taps, void* stream) {
     return op_pack_conv_w(w, dtype, H(out), Cout, Cin, taps, S(stream));

@@ -329,6 +329,25 @@ __global__ void pack_conv_w_dup_kernel(const void* __restrict__ w, int dt, half_
         out[i] = to_h_checked(load_as_f32(w, (co * Cin + ci) * taps + tp, dt), ovf);
     }
 }
+// phase form of a 3x3 conv over a nearest x2 up-sampled map (igemm.hip: IG_CONV2D_PHASE): out[ph = 2a + b][co][t = 2ty + tx][ci] =
+// sum of w[co][ci][ky][kx] over ky in S(a, ty), kx in S(b, tx), S(0,0) = {0}, S(0,1) = {1,2}, S(1,0) = {0,1}, S(1,1) = {2} -- the 3x3
+// window of output pixel (2i + a, 2j + b) touches source rows i + a - 1 + ty only.  fp32 sums in (ky, kx) order, rounded once
+__global__ void pack_conv_w_phase_kernel(const void* __restrict__ w, int dt, half_t* __restrict__ out, int Cout, int Cin, int* ovf) {
+    const size_t per = (size_t)Cout * 4 * Cin, total = 4 * per;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int ci = (int)(i % Cin);
+        const size_t r = i / Cin;
+        const int t = (int)(r & 3), ty = t >> 1, tx = t & 1;
+        const size_t co = (r >> 2) % Cout;
+        const int ph = (int)(i / per), a = ph >> 1, b = ph & 1;
+        const int ky0 = a + ty == 0 ? 0 : (a + ty == 2 ? 2 : (a ? 0 : 1)), ky1 = a + ty == 1 ? ky0 + 1 : ky0;
+        const int kx0 = b + tx == 0 ? 0 : (b + tx == 2 ? 2 : (b ? 0 : 1)), kx1 = b + tx == 1 ? kx0 + 1 : kx0;
+        float s = 0.f;
+        for (int ky = ky0; ky <= ky1; ++ky)
+            for (int kx = kx0; kx <= kx1; ++kx) s += load_as_f32(w, (co * Cin + ci) * 9 + ky * 3 + kx, dt);
+        out[i] = to_h_checked(s, ovf);
+    }
+}
 __global__ void pack_conv_w_direct_kernel(const void* __restrict__ w, int dt, float* __restrict__ out, int Cout, int Cin) {
     const size_t total = (size_t)9 * Cin * Cout;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
@@ -539,6 +558,10 @@ int op_pack_conv_w(const void* w, int dtype, half_t* out, int Cout, int Cin, int
 }
 int op_pack_conv_w_dup(const void* w, int dtype, half_t* out, int Cout, int Cin, int taps, hipStream_t s, int* ovf) {
     LAUNCH("pack", pack_conv_w_dup_kernel, dim3(grid_for((size_t)Cout * Cin * taps * 2)), dim3(256), 0, s, w, dtype, out, Cout, Cin, taps, ovf);
+    return 0;
+}
+int op_pack_conv_w_phase(const void* w, int dtype, half_t* out, int Cout, int Cin, hipStream_t s, int* ovf) {
+    LAUNCH("pack", pack_conv_w_phase_kernel, dim3(grid_for((size_t)Cout * Cin * 16)), dim3(256), 0, s, w, dtype, out, Cout, Cin, ovf);
     return 0;
 }
 int op_pack_conv_w_direct(const void* w, int dtype, float* out, int Cout, int Cin, hipStream_t s) {

@@ -69,6 +69,9 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (MinWaves<BM, BN, WAVES_M *
     const int gbid = blockIdx.x - gp * per;                                //  the descriptor below is read with scalar loads)
     if (gbid >= ntm * ntn * splitk) return;
     const IGemmArgs& a = IGEMM_GROUP_ARGS(gp);
+    // PHASE (IG_CONV2D_PHASE): the tile rows are four padded phase blocks of ntm / 4 tiles each; a tile lies in ONE phase `ph` = 2 (oy & 1)
+    // + (ox & 1), m0 is its first row INSIDE the phase: row m = (n Hin + i) Win + j of the source grid, output pixel (2i + a, 2j + b)
+    constexpr bool PHASE = MODE == IG_CONV2D_PHASE, CONVLIKE = MODE == IG_CONV2D || PHASE;
     constexpr int NT = WAVES_M * WAVES_N * 64, NW = NT / 64;
     constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;   // per-wave tile
     constexpr int MI = WM / 16, NI = WN / 16;
@@ -93,9 +96,11 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (MinWaves<BM, BN, WAVES_M *
     const int split = gbid / nblk;
     const int first_bid = gbid - split * nblk;
     int m0, n0;                          // origin of the output tile being ACCUMULATED (the epilogue's tile)
+    int ph = 0;
     {
         int tile_m, tile_n;
         tileorder::tile_of(first_bid, ntm, ntn, order, &tile_m, &tile_n);
+        if (PHASE) { const int tpp = ntm >> 2; ph = tile_m / tpp; tile_m -= ph * tpp; }
         m0 = tile_m * BM;
         n0 = tile_n * BN;
     }
@@ -110,15 +115,16 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (MinWaves<BM, BN, WAVES_M *
     size_t b_off[BPASS];
     bool b_ok[BPASS];
     int b_c8[BPASS];
-    const int VH = a.Hin * a.up, VW = a.Win * a.up;   // virtual (up-sampled) input grid
-    const int ushift = (a.up == 2) ? 1 : 0;
+    const int VH = PHASE ? a.Hin : a.Hin * a.up, VW = PHASE ? a.Win : a.Win * a.up;   // virtual (up-sampled) input grid; PHASE: the source grid
+    const int ushift = (!PHASE && a.up == 2) ? 1 : 0;
+    const int Mrows = PHASE ? (a.M >> 2) : a.M;       // GEMM rows a tile row index is checked against (PHASE: the rows of one phase)
     auto set_stage_tile = [&](const int sm0, const int sn0) {
 #pragma unroll
         for (int i = 0; i < APASS; ++i) {
             const int trow = (i * NW + wave) * RPW + lrow;
             a_c8[i] = (lpos ^ chunk_swz<BK>(trow)) * 8;
             const int m = sm0 + trow;
-            a_ok[i] = m < a.M;
+            a_ok[i] = m < Mrows;
             const int mm = a_ok[i] ? m : 0;
             if (MODE == IG_ROWS) {
                 a_off[i] = (size_t)mm * a.lda;
@@ -130,6 +136,11 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (MinWaves<BM, BN, WAVES_M *
                 a_off[i] = (size_t)n * a.Hin * a.Win;
                 a_y[i] = oy * a.stride - pad;
                 a_x[i] = ox * a.stride - pad;
+            } else if (PHASE) {
+                const int q = mm / a.Win, n = q / a.Hin;      // q = n Hin + i
+                a_off[i] = (size_t)n * a.Hin * a.Win;
+                a_y[i] = q - n * a.Hin + (ph >> 1) - 1;       // tap (ty, tx) reads source pixel (i + a - 1 + ty, j + b - 1 + tx)
+                a_x[i] = mm - q * a.Win + (ph & 1) - 1;
             } else {
                 const int fr = mm / a.HW;
                 if (a.t_pad) {
@@ -156,7 +167,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (MinWaves<BM, BN, WAVES_M *
     set_stage_tile(m0, n0);
 
     const half_t* Aptr = (const half_t*)a.A;
-    const half_t* Wptr = (const half_t*)a.W;
+    const half_t* Wptr = (const half_t*)a.W + (PHASE ? (size_t)ph * a.Nout * a.Ktot : 0);      // PHASE: W = [4 phases][Nout][4 taps][Cin]
     const half_t* Rptr = (const half_t*)a.res;
 
     typedef const void __attribute__((address_space(1)))* gptr_t;
@@ -191,6 +202,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (MinWaves<BM, BN, WAVES_M *
         } else if (MODE != IG_ROWS) { tap = k0 / a.Cin; c0 = k0 - tap * a.Cin; }
         int ky = 0, kx = 0;
         if (MODE == IG_CONV2D && a.taps == 9) { ky = tap / 3; kx = tap - 3 * ky; }
+        if (PHASE) { ky = tap >> 1; kx = tap & 1; }
         half_t* Ab = As + buf * BM * BK;
         half_t* Bb = Bs + bbuf * BNP * BK;
 #pragma unroll
@@ -199,7 +211,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (MinWaves<BM, BN, WAVES_M *
             size_t off;
             if (MODE == IG_ROWS) {
                 off = a_off[i] + (paired ? c0 : k0) + a_c8[i];
-            } else if (MODE == IG_CONV2D) {
+            } else if (CONVLIKE) {
                 const int vy = a_y[i] + ky, vx = a_x[i] + kx;
                 ok = ok && vy >= 0 && vy < VH && vx >= 0 && vx < VW;
                 const int sy = vy >> ushift, sx = vx >> ushift;
@@ -346,7 +358,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (MinWaves<BM, BN, WAVES_M *
 
     }
 
-    igemm_epilogue<BM, BN, WAVES_M, WAVES_N, SWAP, MinWaves<BM, BN, NW>::v>(a, acc, m0, n0, wm, wn, lane, wave, split, epi_smem);
+    igemm_epilogue<BM, BN, WAVES_M, WAVES_N, SWAP, MinWaves<BM, BN, NW>::v, PHASE>(a, acc, m0, n0, wm, wn, lane, wave, split, epi_smem, ph);
 }
 
 // =====================================================================================================================
@@ -404,6 +416,7 @@ __global__ __launch_bounds__(512, 2) void igemm8_kernel(IGemmGroup kargs, int pe
     const int gbid = blockIdx.x - gp * per;
     if (gbid >= ntm * ntn * splitk) return;
     const IGemmArgs& a = IGEMM_GROUP_ARGS(gp);
+    constexpr bool PHASE = MODE == IG_CONV2D_PHASE, CONVLIKE = MODE == IG_CONV2D || PHASE;      // PHASE: see igemm_kernel
     // in-launch split-K reduction (red_off != -1): fragment slabs at the start of the problem's split-K scratch; ticket words at red_off
     // inside it, or (red_off == -2) the descriptor's own zeroed ticket words
     float* const red_ws = (float*)a.splitk_ws;
@@ -420,9 +433,11 @@ __global__ __launch_bounds__(512, 2) void igemm8_kernel(IGemmGroup kargs, int pe
     const int split = gbid / nblk;
     const int first_bid = gbid - split * nblk;
     int m0, n0;
+    int ph = 0;
     {
         int tile_m, tile_n;
         tileorder::tile_of(first_bid, ntm, ntn, order, &tile_m, &tile_n);
+        if (PHASE) { const int tpp = ntm >> 2; ph = __builtin_amdgcn_readfirstlane(tile_m / tpp); tile_m -= ph * tpp; }
         m0 = tile_m * BM;
         n0 = tile_n * BN;
     }
@@ -441,14 +456,15 @@ __global__ __launch_bounds__(512, 2) void igemm8_kernel(IGemmGroup kargs, int pe
     // the chunk swizzle of LDS row j is (j >> 1) & 7 = ((wave & 1) * 4 + lrow / 2) & 7 for every pass: one swizzled source chunk per lane
     const int c8b = ((lpos ^ ((((wave & 1) << 2) + (lrow >> 1)) & 7)) * 8) * 2;        // bytes
     const int pad = (a.taps == 9 && !a.tap_origin) ? 1 : 0;     // tap_origin 1: taps start at stride*o (Downsample2D)
-    const int VH = a.Hin * a.up, VW = a.Win * a.up;
-    const int ushift = (a.up == 2) ? 1 : 0;
+    const int VH = PHASE ? a.Hin : a.Hin * a.up, VW = PHASE ? a.Win : a.Win * a.up;      // PHASE: the taps walk the source grid
+    const int ushift = (!PHASE && a.up == 2) ? 1 : 0;
     const int lda2 = (int)a.lda * 2;
     // per staged A row (sub-block sb, pass i = wave row): tile row i*128 + sb*64 + wave*8 + lane/8
     //   ROWS     a_st = byte offset of the row's chunk, or OOB beyond M
     //   TEMPORAL a_st = that offset (a multiple of 16) | bit t set when frame tap t of the row exists (bit 1 = the row itself)
     //   CONV2D   a_st = image << 24 | (oy*stride - pad + 1) << 12 | (ox*stride - pad + 1)   (y field 0xfff beyond M: never in bounds);
     //            a_cur = the offsets of the tap being walked (recomputed when a sub-block's tap changes: once per Cin / 64 k-tiles)
+    //   PHASE    a_st = image << 24 | (i + a) << 12 | (j + b) of row m = (n Hin + i) Win + j of phase (a, b): the same packing, 2x2 taps
     unsigned a_st[2][2], a_cur[2][2];
     int cur_tap[2] = {-1, -1};
 #pragma unroll
@@ -456,7 +472,7 @@ __global__ __launch_bounds__(512, 2) void igemm8_kernel(IGemmGroup kargs, int pe
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int m = m0 + i * 128 + sb * 64 + wave * 8 + lrow;
-            const bool ok = m < a.M;
+            const bool ok = m < (PHASE ? (a.M >> 2) : a.M);
             const int mm = ok ? m : 0;
             a_cur[sb][i] = g8::OOB;
             if (MODE == IG_ROWS) {
@@ -467,6 +483,10 @@ __global__ __launch_bounds__(512, 2) void igemm8_kernel(IGemmGroup kargs, int pe
                 const int oy = rem / a.Wout, ox = rem - oy * a.Wout;
                 const int yf = ok ? oy * a.stride - pad + 1 : 0xfff;
                 a_st[sb][i] = ((unsigned)n << 24) | ((unsigned)yf << 12) | (unsigned)(ox * a.stride - pad + 1);
+            } else if (PHASE) {
+                const int q = mm / a.Win, n = q / a.Hin;      // q = n Hin + i
+                const int yf = ok ? q - n * a.Hin + (ph >> 1) : 0xfff;
+                a_st[sb][i] = ((unsigned)n << 24) | ((unsigned)yf << 12) | (unsigned)(mm - q * a.Win + (ph & 1));
             } else {
                 const int fr = mm / a.HW;
                 unsigned base, bits;
@@ -489,7 +509,8 @@ __global__ __launch_bounds__(512, 2) void igemm8_kernel(IGemmGroup kargs, int pe
     const unsigned b0_vo = (unsigned)((n0 + ((wave * 8 + lrow) >> 4) * WN + ((wave * 8 + lrow) & 15)) * ldw2 + c8b);
     const unsigned b1_vo = b0_vo + 32u * (unsigned)ldw2;
     const __amdgpu_buffer_rsrc_t a_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.A), 0, (int)0x80000000u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t w_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.W), 0, (int)0x80000000u, 0x00020000);
+    // (PHASE: W = [4 phases][Nout][4 taps][Cin], the tile's phase block)
+    const __amdgpu_buffer_rsrc_t w_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>((const half_t*)a.W + (PHASE ? (size_t)ph * a.Nout * a.Ktot : 0)), 0, (int)0x80000000u, 0x00020000);
 
     // position of a k-tile in the K axis: tap, channel offset of the A chunk (bytes), k offset in a weight row (bytes).  The stream
     // is staged in order, so positions advance incrementally (no division per k-tile)
@@ -533,10 +554,11 @@ __global__ __launch_bounds__(512, 2) void igemm8_kernel(IGemmGroup kargs, int pe
     // A half-tile sb of the k-tile at p -> buffer buf
     auto stage_a = [&](const int sb, const KPos p, const int buf) __attribute__((always_inline)) {
         const int dst = ((sb ? L::A1 : L::A0) ^ (buf ? L::TOG_A : 0)) + wave * 1024;
-        if (MODE == IG_CONV2D && p.tap != cur_tap[sb]) {
+        if (CONVLIKE && p.tap != cur_tap[sb]) {
             cur_tap[sb] = p.tap;
             int ky = 0, kx = 0;
-            if (a.taps == 9) { ky = (p.tap * 11) >> 5; kx = p.tap - 3 * ky; }
+            if (PHASE) { ky = p.tap >> 1; kx = p.tap & 1; }
+            else if (a.taps == 9) { ky = (p.tap * 11) >> 5; kx = p.tap - 3 * ky; }
             const int hwin = a.Hin * a.Win;
             // (the operands are made opaque here: hoisted out of the k-loop, the unpacked fields of a_st cost eight more registers
             // than the loop has, and their spill reloads drain the DMA queue)
@@ -563,7 +585,7 @@ __global__ __launch_bounds__(512, 2) void igemm8_kernel(IGemmGroup kargs, int pe
             unsigned vo;
             if (MODE == IG_ROWS) {
                 vo = a_st[sb][i];
-            } else if (MODE == IG_CONV2D) {
+            } else if (CONVLIKE) {
                 vo = a_cur[sb][i];
             } else {
                 const unsigned st = a_st[sb][i];
@@ -764,7 +786,7 @@ __global__ __launch_bounds__(512, 2) void igemm8_kernel(IGemmGroup kargs, int pe
         }
         slab = 0;
     }
-    igemm_epilogue<BM, BN, 2, 4, true, 1>(a, acc, m0, n0, wm, wn, lane, wave, slab, smem_raw);
+    igemm_epilogue<BM, BN, 2, 4, true, 1, PHASE>(a, acc, m0, n0, wm, wn, lane, wave, slab, smem_raw, ph);
 }
 
 // split-K tail: out = epilogue( sum_s slab[s] ), 8 consecutive columns per thread (row-major outputs only)
@@ -928,14 +950,19 @@ bool can_use8(const IGemmArgs& a, bool swap) {
     if (!igemm8_mode() || !swap) return false;
     if (a.Cin % 64 != 0 || (a.a_split == 2 && ((a.Cin / 2) % 64 != 0 || a.mode == IG_TEMPORAL))) return false;
     // conv rows are packed as image (8 bits) | y + 1 (12 bits) | x + 1 (12 bits)
-    if (a.mode == IG_CONV2D && ((double)a.M / ((double)a.Hout * a.Wout) > 256.0 || a.Hin * a.up > 4000 || a.Win * a.up > 4000 ||
-                                 a.Hout * a.stride > 4000 || a.Wout * a.stride > 4000)) return false;
+    const bool convlike = a.mode == IG_CONV2D || a.mode == IG_CONV2D_PHASE;
+    if (convlike && ((double)a.M / ((double)a.Hout * a.Wout) > 256.0 || a.Hin * a.up > 4000 || a.Win * a.up > 4000 ||
+                     a.Hout * a.stride > 4000 || a.Wout * a.stride > 4000)) return false;
     double abytes;
-    if (a.mode == IG_CONV2D) abytes = (double)a.M / ((double)a.Hout * a.Wout) * a.Hin * a.Win * a.lda * 2.0;
+    if (convlike) abytes = (double)a.M / ((double)a.Hout * a.Wout) * a.Hin * a.Win * a.lda * 2.0;
     else if (a.mode == IG_TEMPORAL && a.t_pad) abytes = ((double)a.M + 2.0 * a.HW * ((double)a.M / ((double)a.F * a.HW))) * a.lda * 2.0;
     else abytes = (double)a.M * a.lda * 2.0;
-    return abytes < 2147483648.0 && (double)a.Nout * a.Ktot * 2.0 < 2147483648.0;
+    return abytes < 2147483648.0 && (double)a.Nout * a.Ktot * 2.0 < 2147483648.0;      // (PHASE: per phase block of the pack)
 }
+
+// GEMM rows of the tile grid: M, or for the phase form the rows of ONE phase -- its grid is four padded blocks of ceil(rows / BM) tiles
+inline int grid_rows(const IGemmArgs& a) { return a.mode == IG_CONV2D_PHASE ? a.M / 4 : a.M; }
+inline int grid_ntm(const IGemmArgs& a, int bm) { return (a.mode == IG_CONV2D_PHASE ? 4 : 1) * ((grid_rows(a) + bm - 1) / bm); }
 
 // first column of the transposed last segment of a MIXED segment list on the vector epilogue (0 = not such a problem): every tile must
 // lie in one segment, so only tile widths that divide it may be chosen
@@ -959,6 +986,7 @@ inline size_t splitk_twords(const IGemmArgs& a, int sk) { return wide_tiles(a) *
 // number of K splits for this problem (1 = none); `use8` = can_use8(a)
 int splitk_factor(const IGemmArgs& a, bool use8) {
     if (a.geglu || a.nseg != 1 || a.seg[0].fmt != SEG_ROW || a.Nout % 64 != 0 || a.Cin % 32 != 0 || a.mode == IG_TEMPORAL) return 1;
+    if (a.mode == IG_CONV2D_PHASE) return 1;      // (its tile grid is per phase: the split-K slabs and tickets are not laid out for it)
     if (a.Nout % wide_bn(a) != 0) return 1;
     const long tiles = (long)wide_tiles(a);
     const int nk32 = a.Ktot / 32;
@@ -978,7 +1006,9 @@ int splitk_factor(const IGemmArgs& a, bool use8) {
 }
 
 // ---- the kernel forms ----
-// THE list of instantiated tiles; every entry exists in the three gather modes.
+// THE list of instantiated tiles; every entry exists in the three gather modes IG_ROWS, IG_CONV2D and IG_TEMPORAL.  The phase form
+// (IG_CONV2D_PHASE) exists for the tiles its selection can reach -- the two wide tiles and the BK = 64 ring tiles (kPhaseTile) --
+// a nullptr elsewhere.
 //   W(id, NI)                                                    the 8-phase wide tile, 256 x 64 NI x 64 (vector epilogue)
 //   R(id, force, BM, BN, BK, WAVES_M, WAVES_N, NSTAGE)           a ring tile in the SWAP = true form (vector epilogue) only
 //   B(id, force, BM, BN, BK, WAVES_M, WAVES_N, NSTAGE)           a ring tile with both epilogues: entry id (vector), then id + 1 (scalar)
@@ -1005,7 +1035,7 @@ struct Tile {
     const char* force;
     int threads;
     size_t smem;                              // dynamic LDS
-    const void* kern[3];                      // by gather mode (IG_ROWS, IG_CONV2D, IG_TEMPORAL)
+    const void* kern[4];                      // by gather mode (IG_ROWS, IG_CONV2D, IG_TEMPORAL, IG_CONV2D_PHASE: nullptr = not instantiated)
 };
 template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int NSTAGE>
 constexpr size_t ring_smem() {
@@ -1028,17 +1058,23 @@ constexpr size_t wide_smem() {
 #define TILE_ID_B(id, ...) id, id##_scalar,
 enum TileId { IGEMM_TILES(TILE_ID_W, TILE_ID_R, TILE_ID_B) kNumTiles };
 #define RING_KERN(MODE, SWAP, ...) (const void*)igemm_kernel<__VA_ARGS__, MODE, SWAP>
+template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int NSTAGE, bool SWAP>
+constexpr const void* ring_phase_kern() {
+    if constexpr (BK == 64) return (const void*)igemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, NSTAGE, IG_CONV2D_PHASE, SWAP>;
+    else return nullptr;
+}
 #define TILE_RING(force, SWAP, BM, BN, BK, WM, WN, NS)                                                               \
     {0, BM, BN, BK, WM, WN, NS, SWAP, force, WM * WN * 64, ring_smem<BM, BN, BK, WM, WN, NS>(),                      \
      {RING_KERN(IG_ROWS, SWAP, BM, BN, BK, WM, WN, NS), RING_KERN(IG_CONV2D, SWAP, BM, BN, BK, WM, WN, NS),         \
-      RING_KERN(IG_TEMPORAL, SWAP, BM, BN, BK, WM, WN, NS)}},
+      RING_KERN(IG_TEMPORAL, SWAP, BM, BN, BK, WM, WN, NS), ring_phase_kern<BM, BN, BK, WM, WN, NS, SWAP>()}},
 #define TILE_W(id, NI)                                                                                               \
     {NI, 256, 64 * NI, 64, 0, 0, 0, true, nullptr, 512, wide_smem<NI>(),                                             \
-     {(const void*)igemm8_kernel<NI, IG_ROWS>, (const void*)igemm8_kernel<NI, IG_CONV2D>, (const void*)igemm8_kernel<NI, IG_TEMPORAL>}},
+     {(const void*)igemm8_kernel<NI, IG_ROWS>, (const void*)igemm8_kernel<NI, IG_CONV2D>, (const void*)igemm8_kernel<NI, IG_TEMPORAL>,     \
+      (const void*)igemm8_kernel<NI, IG_CONV2D_PHASE>}},
 #define TILE_R(id, force, ...) TILE_RING(force, true, __VA_ARGS__)
 #define TILE_B(id, force, ...) TILE_RING(force, true, __VA_ARGS__) TILE_RING(force, false, __VA_ARGS__)
 const Tile kTiles[kNumTiles] = {IGEMM_TILES(TILE_W, TILE_R, TILE_B)};
-static_assert(IG_ROWS == 0 && IG_CONV2D == 1 && IG_TEMPORAL == 2, "Tile::kern is indexed by the gather mode");
+static_assert(IG_ROWS == 0 && IG_CONV2D == 1 && IG_TEMPORAL == 2 && IG_CONV2D_PHASE == 3, "Tile::kern is indexed by the gather mode");
 
 // ---- selection: everything that is decided about a launch, decided in one place and without a device ----
 enum { RED_NONE = 0, RED_FINISH = 1, RED_INLAUNCH = 2 };
@@ -1062,7 +1098,7 @@ IGemmForm igemm_select(const IGemmArgs& a, int group_n, bool pinned = false) {
     auto al = [&](int bn) { return mb == 0 || mb % bn == 0; };
     auto form = [&](int t, int sk = 1) {
         const Tile& T = kTiles[t];
-        IGemmForm f = {t, sk, RED_NONE, false, plan_order(a, T.ni != 0, T.bn, (a.M + T.bm - 1) / T.bm, (a.Nout + T.bn - 1) / T.bn)};
+        IGemmForm f = {t, sk, RED_NONE, false, plan_order(a, T.ni != 0, T.bn, grid_ntm(a, T.bm), (a.Nout + T.bn - 1) / T.bn)};
         if (sk > 1) {
             // CTRL_SPLITK_INLAUNCH: 0 = always the finish kernel; default = in-launch for 2..4 splits; "all" = also the two-level form for 5..16
             // splits -- built and measured in round 6, NOT the default: the last arrivers read their <= 4 slabs of 256-320 KB alone, at the
@@ -1086,7 +1122,7 @@ IGemmForm igemm_select(const IGemmArgs& a, int group_n, bool pinned = false) {
     // (a grouped launch fills the chip with all its problems: the tile is sized for the group, unless the caller wants every problem
     // computed with the tile it would get alone -- ctrl_group_launches(2), bit-identical to one-by-one launches)
     const long gmul = group_tiles_as_alone() ? 1 : group_n;
-    auto tiles = [&](int bm, int bn) { return gmul * (long)((a.M + bm - 1) / bm) * ((a.Nout + bn - 1) / bn); };
+    auto tiles = [&](int bm, int bn) { return gmul * (long)grid_ntm(a, bm) * ((a.Nout + bn - 1) / bn); };      // (phase form: the padded grid)
     auto eff = [&](int bn) { return (double)a.Nout / (double)(((a.Nout + bn - 1) / bn) * bn); };
     // 256x256 (8 waves, 128x64 per wave): fewest LDS bytes per FLOP -- the limiter of the smaller tiles on this chip
     // split-K: small-M / long-K problems (the ControlNet's low-resolution 3x3 convs) leave most CUs idle with 256-row
@@ -1133,10 +1169,13 @@ IGemmForm igemm_select(const IGemmArgs& a, int group_n, bool pinned = false) {
         if (a.Nout % 320 == 0 && (tiles(256, 320) >= 160 || force8) && !a.geglu && al(320)) return form(W5);
         if (a.Nout % 256 == 0 && (tiles(256, 256) >= 200 || force8) && al(256)) return form(W4);
     }
+    // (the phase form is like IG_CONV2D with Ktot = 4 Cin from here on, minus the BK = 32 ring tiles: Cin % 64 == 0 is a precondition
+    // of the form, so it only gets here with the wide tiles switched off or a grid too small for them)
+    const bool phase = a.mode == IG_CONV2D_PHASE;
     // (vector-epilogue variant only: the scalar-epilogue one does not fit the register file at this tile size)
-    if (tiles(256, 256) >= 200 && eff(256) > 0.9 && swap && al(256)) return form(T256x256);
+    if (!phase && tiles(256, 256) >= 200 && eff(256) > 0.9 && swap && al(256)) return form(T256x256);
     // N = 320 / 640 / 960 / 1280 / 1920 / 3840 (every conv and QKV width of the path): 256x320 tile, 128x80 per wave
-    if (a.Nout % 320 == 0 && tiles(256, 320) >= 160 && swap && !a.geglu && al(320)) return form(T256x320);
+    if (!phase && a.Nout % 320 == 0 && tiles(256, 320) >= 160 && swap && !a.geglu && al(320)) return form(T256x320);
     if (!bk64) {
         if (tiles(128, 128) >= 192 && al(128)) return either(T128x128x32);
         return either(T64x64x32);
@@ -1199,7 +1238,7 @@ void prof_igemm(const IGemmForm& f, const IGemmArgs& a, int G) {
     char grp[16] = "", extra[40], sym[96];
     if (G > 1) snprintf(grp, sizeof(grp), " x%d", G);
     form_splitk_note(f, extra, sizeof(extra));
-    prof_detail("M%d N%d K%d taps%d%s%s%s%s", a.M, a.Nout, a.Ktot, a.taps, a.a_split ? " split-A" : "", a.geglu ? " geglu" : "", extra, grp);
+    prof_detail("M%d N%d K%d taps%d%s%s%s%s%s", a.M, a.Nout, a.Ktot, a.taps, a.mode == IG_CONV2D_PHASE ? " phase" : "", a.a_split ? " split-A" : "", a.geglu ? " geglu" : "", extra, grp);
     form_symbol(f, a.mode, sym, sizeof(sym));
     prof_symbol("%s", sym);
 }
@@ -1209,7 +1248,8 @@ int launch(const IGemmForm& f, const IGemmArgs* probs, int n, hipStream_t s) {
     const IGemmArgs& a = probs[0];
     const Tile& T = kTiles[f.tile];
     const void* const kern = T.kern[a.mode];
-    static bool attr_done[kNumTiles][3][kMaxDevices] = {};       // function attributes are per device
+    CTRL_CHECK(kern != nullptr, "igemm: the selected tile has no kernel for this gather mode");
+    static bool attr_done[kNumTiles][4][kMaxDevices] = {};       // function attributes are per device
     bool& done = attr_done[f.tile][a.mode][cur_device()];
     if (!done) {
         HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)T.smem));
@@ -1220,7 +1260,7 @@ int launch(const IGemmForm& f, const IGemmArgs* probs, int n, hipStream_t s) {
         zeros = zero_page();
         CTRL_CHECK(zeros != nullptr, "igemm: could not allocate the zero page");
     }
-    int ntm = (a.M + T.bm - 1) / T.bm, ntn = (a.Nout + T.bn - 1) / T.bn, splitk = f.splitk, order = f.order;
+    int ntm = grid_ntm(a, T.bm), ntn = (a.Nout + T.bn - 1) / T.bn, splitk = f.splitk, order = f.order;
     // workgroups per problem: a group pads them to a multiple of 8 (XCD of a workgroup = its local index % 8, tile_order.h)
     int per = ntm * ntn * splitk;
     if (n > 1) per = (per + 7) & ~7;
@@ -1235,7 +1275,7 @@ int launch(const IGemmForm& f, const IGemmArgs* probs, int n, hipStream_t s) {
     prof_igemm(f, a, n);
     void* ring_args[] = {&grp, &per, &ntm, &ntn, &zeros, &splitk, &order};
     void* wide_args[] = {&grp, &per, &ntm, &ntn, &splitk, &order, &red_off};
-    const char* tag = a.mode == IG_ROWS ? "igemm_rows" : (a.mode == IG_CONV2D ? "igemm_conv" : "igemm_temporal");
+    const char* tag = a.mode == IG_ROWS ? "igemm_rows" : (a.mode == IG_TEMPORAL ? "igemm_temporal" : "igemm_conv");
     if (g_prof_on) prof_before(tag, "igemm", (long)per * n * T.threads, s);
     (void)hipLaunchKernel(kern, dim3(per * n), dim3(T.threads), T.ni ? wide_args : ring_args, T.smem, s);
     if (g_prof_on) prof_after(s);
@@ -1397,12 +1437,23 @@ static int igemm_validate(const IGemmArgs& a) {
         CTRL_CHECK(a.taps == 9 || a.taps == 1, "igemm conv2d: taps must be 1 or 9");
         CTRL_CHECK((a.up == 1 || a.up == 2) && (a.stride == 1 || a.stride == 2), "igemm conv2d: up/stride must be 1|2");
         CTRL_CHECK(a.tap_origin == 0 || (a.tap_origin == 1 && a.taps == 9), "igemm conv2d: tap_origin must be 0, or 1 for a 3x3 conv");
+    } else if (a.mode == IG_CONV2D_PHASE) {
+        CTRL_CHECK(a.taps == 4 && a.up == 2 && a.stride == 1 && a.tap_origin == 0, "igemm conv2d phase form: taps = 4, up = 2, stride = 1, tap_origin = 0");
+        CTRL_CHECK(a.Hin > 0 && a.Win > 0 && a.Hout == 2 * a.Hin && a.Wout == 2 * a.Win && a.M % (a.Hout * a.Wout) == 0 &&
+                   a.rows_per_img == a.Hout * a.Wout,
+                   "igemm conv2d phase form: Hout = 2 Hin, Wout = 2 Win, M = images * Hout * Wout, rows_per_img = Hout * Wout");
+        CTRL_CHECK(a.Cin % 64 == 0, "igemm conv2d phase form: Cin must be a multiple of 64");
+        CTRL_CHECK(a.a_split == 0 && !a.res && a.res_up == 0 && !a.geglu && !a.blend_mix && !a.scale2_from,
+                   "igemm conv2d phase form: no split operand, residual, GEGLU, blend or scale2 range");
+        for (int i = 0; i < a.nseg; ++i) CTRL_CHECK(a.seg[i].fmt == SEG_ROW, "igemm conv2d phase form: row-major outputs only");
     } else if (a.mode == IG_TEMPORAL) {
         CTRL_CHECK(a.taps == 3 && a.F > 0 && a.HW > 0, "igemm temporal: taps must be 3");
+    } else if (a.mode != IG_ROWS) {
+        CTRL_FAIL("igemm: unknown mode " + std::to_string(a.mode));
     } else {
         CTRL_CHECK(a.taps == 1, "igemm rows: taps must be 1");
     }
-    CTRL_CHECK(a.tap_origin == 0 || a.mode == IG_CONV2D, "igemm: tap_origin applies to conv2d problems only");
+    CTRL_CHECK(a.tap_origin == 0 || a.mode == IG_CONV2D || a.mode == IG_CONV2D_PHASE, "igemm: tap_origin applies to conv2d problems only");
     return 0;
 }
 

@@ -76,10 +76,21 @@ __device__ __forceinline__ IGemmSeg seg_select(const IGemmArgs& e, int si) {
 // ---------------- epilogue of an accumulated tile (m0, n0), shared by every main loop of this file ----------------
 // acc[mi][ni]: the 16x16 fragments of the wave tile (WM x WN at wave position (wm, wn)); epi_smem: the workgroup's LDS, dead
 // as a k-loop ring when this runs (the caller has NOT synchronised: the first thing the staged forms do is a barrier).
-template <int BM, int BN, int WAVES_M, int WAVES_N, bool SWAP, int MINW>
+// PHASE (igemm.hip: IG_CONV2D_PHASE; row-major outputs only): the tile's rows are rows of ONE output phase ph = 2a + b -- row m =
+// (n Hin + i) Win + j of the source grid stands for output pixel (2i + a, 2j + b).  Rows are valid below M / 4, the per-image vector
+// changes every Hin Win rows, and everything that is STORED by output row goes to phase_out_row(m).
+__device__ __forceinline__ int phase_out_row(const IGemmArgs& e, int m, int ph) {
+    const int q = m / e.Win;                              // n Hin + i: (n Hout + 2i + a) Wout + 2j + b = (2q + a) Wout + 2 (m - q Win) + b
+    return (2 * q + (ph >> 1)) * e.Wout + 2 * (m - q * e.Win) + (ph & 1);
+}
+template <int BM, int BN, int WAVES_M, int WAVES_N, bool SWAP, int MINW, bool PHASE = false>
 __device__ __forceinline__ void igemm_epilogue(const IGemmArgs& e, f4 (&acc)[BM / WAVES_M / 16][BN / WAVES_N / 16], const int m0, const int n0,
-                                               const int wm, const int wn, const int lane, const int wave, const int split, char* const epi_smem) {
+                                               const int wm, const int wn, const int lane, const int wave, const int split, char* const epi_smem,
+                                               const int ph = 0) {
     constexpr int NW = WAVES_M * WAVES_N;
+    const int Mrows = PHASE ? (e.M >> 2) : e.M;                        // rows of the tile's row space
+    const int rpi = PHASE ? e.Hin * e.Win : e.rows_per_img;           // ... per image (the per-image vector)
+    auto out_row = [&](int row) __attribute__((always_inline)) { return PHASE ? phase_out_row(e, row, ph) : row; };
     constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;
     constexpr int MI = WM / 16, NI = WN / 16;
     const half_t* Rptr = (const half_t*)e.res;
@@ -191,18 +202,20 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmArgs& e, f4 (&acc)[BM 
             // column-only terms, fetched once per tile (or per image): cv = bias + the per-image vector while the 16 rows of a slab
             // share an image (slabs start at multiples of 16); ONE register vector per fragment column -- the 80-wide wave tile
             // has no room for two
-            const bool rv_uniform = MINW == 1 && e.rowvec && (e.rows_per_img % 16) == 0;      // (MINW > 1: the 128-register tiles spill with it)
+            const bool rv_uniform = MINW == 1 && e.rowvec && (rpi % 16) == 0;      // (MINW > 1: the 128-register tiles spill with it)
             f4 cv[NI];
+            const int img_last = PHASE ? (Mrows - 1) / rpi : 0;
             auto load_cv = [&](int img) __attribute__((always_inline)) {
 #pragma unroll
                 for (int ni = 0; ni < NI; ++ni) {
                     const int pcb = n0 + wn * WN + ni * 16;
                     cv[ni] = (e.bias && pcb < e.Nout) ? *(const f4*)(e.bias + pcb + ecol) : f4{0.f, 0.f, 0.f, 0.f};
-                    if (rv_uniform && pcb < e.Nout && !(gg && (ni & 1))) cv[ni] += *(const f4*)(e.rowvec + (size_t)img * e.rowvec_ld + pcb + ecol);
+                    // (PHASE: every phase block ends in padding rows -- their image index is kept inside the vector's rows)
+                    if (rv_uniform && pcb < e.Nout && !(gg && (ni & 1))) cv[ni] += *(const f4*)(e.rowvec + (size_t)(PHASE ? min(img, img_last) : img) * e.rowvec_ld + pcb + ecol);
                 }
             };
             int img_cur = 0, img_rem = 0;
-            if (rv_uniform) { img_cur = wrow0 / e.rows_per_img; img_rem = wrow0 - img_cur * e.rows_per_img; }
+            if (rv_uniform) { img_cur = wrow0 / rpi; img_rem = wrow0 - img_cur * rpi; }
             int cv_img = img_cur;
             load_cv(img_cur);
             // the slab loop, for a compile-time number of 8-column pieces per staged row
@@ -247,7 +260,7 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmArgs& e, f4 (&acc)[BM 
                         if (rv_uniform) {
                             if (img_cur != cv_img) { cv_img = img_cur; load_cv(img_cur); }
                             img_rem += 16;
-                            if (img_rem >= e.rows_per_img) { img_rem -= e.rows_per_img; ++img_cur; }
+                            if (img_rem >= rpi) { img_rem -= rpi; ++img_cur; }
                         }
 #pragma unroll
                         for (int ni = 0; ni < NI; ++ni) {
@@ -255,7 +268,7 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmArgs& e, f4 (&acc)[BM 
                             const int pcb = n0 + wn * WN + ni * 16;
                             if (pcb >= e.Nout) continue;
                             f4 x = acc[mi][ni] + cv[ni];
-                            if (!rv_uniform && e.rowvec && row_w < e.M) x += *(const f4*)(e.rowvec + (size_t)(row_w / e.rows_per_img) * e.rowvec_ld + pcb + ecol);
+                            if (!rv_uniform && e.rowvec && row_w < Mrows) x += *(const f4*)(e.rowvec + (size_t)(row_w / rpi) * e.rowvec_ld + pcb + ecol);
                             if (gg) {
                                 const f4 g = acc[mi][ni + (NI > 1 ? 1 : 0)] + cv[ni + 1 < NI ? ni + 1 : ni];
 #pragma unroll
@@ -269,7 +282,7 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmArgs& e, f4 (&acc)[BM 
                             const int lcol = (gg ? (ni >> 1) * 16 : ni * 16) + ecol;
                             const float sc = col_scale(e, wcol0 + lcol);
                             const h4 pk = {(half_t)(x[0] * sc), (half_t)(x[1] * sc), (half_t)(x[2] * sc), (half_t)(x[3] * sc)};
-                            if (e.nonfinite) flag_nonfinite(e.nonfinite, row_w < e.M && (out_of_half(x[0] * sc) || out_of_half(x[1] * sc) || out_of_half(x[2] * sc) || out_of_half(x[3] * sc)));
+                            if (e.nonfinite) flag_nonfinite(e.nonfinite, row_w < Mrows && (out_of_half(x[0] * sc) || out_of_half(x[1] * sc) || out_of_half(x[2] * sc) || out_of_half(x[3] * sc)));
                             *(h4*)(stg16 + erow * RS + lcol * 2) = pk;
                         }
                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -277,10 +290,10 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmArgs& e, f4 (&acc)[BM 
                         for (int t = 0; t < RT; ++t) {
                             const int prt = pr(t);
                             const int row = wrow0 + mi * 16 + prt;
-                            if (!pv(t) || row >= e.M) continue;
+                            if (!pv(t) || row >= Mrows) continue;
                             const int ocol = oc(t);
                             const h8 v = *(const h8*)(stg16 + prt * RS + (ocol - wcol0) * 2);
-                            *(h8*)(outp + ((unsigned)row * old_ + (unsigned)(ocol - ocb))) = v;
+                            *(h8*)(outp + ((unsigned)out_row(row) * old_ + (unsigned)(ocol - ocb))) = v;
                         }
                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                     }
@@ -293,7 +306,7 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmArgs& e, f4 (&acc)[BM 
                     if (rv_uniform) {
                         if (img_cur != cv_img) { cv_img = img_cur; load_cv(img_cur); }      // (wave-uniform) the slab starts a new image
                         img_rem += 16;
-                        if (img_rem >= e.rows_per_img) { img_rem -= e.rows_per_img; ++img_cur; }
+                        if (img_rem >= rpi) { img_rem -= rpi; ++img_cur; }
                     }
 #pragma unroll
                     for (int ni = 0; ni < NI; ++ni) {
@@ -301,7 +314,7 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmArgs& e, f4 (&acc)[BM 
                         const int pcb = n0 + wn * WN + ni * 16;
                         if (pcb >= e.Nout) continue;
                         f4 x = acc[mi][ni] + cv[ni];
-                        if (!rv_uniform && e.rowvec && row_w < e.M) x += *(const f4*)(e.rowvec + (size_t)(row_w / e.rows_per_img) * e.rowvec_ld + pcb + ecol);
+                        if (!rv_uniform && e.rowvec && row_w < Mrows) x += *(const f4*)(e.rowvec + (size_t)(row_w / rpi) * e.rowvec_ld + pcb + ecol);
                         if (gg) {
                             const f4 g = acc[mi][ni + (NI > 1 ? 1 : 0)] + cv[ni + 1 < NI ? ni + 1 : ni];      // the gate's columns = the next fragment's
 #pragma unroll
@@ -320,7 +333,8 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmArgs& e, f4 (&acc)[BM 
                     for (int t = 0; t < RT; ++t) {
                         const int prt = pr(t);
                         const int row = wrow0 + mi * 16 + prt;
-                        if (!pv(t) || row >= e.M) continue;
+                        if (!pv(t) || row >= Mrows) continue;
+                        const int orow = out_row(row);          // where the piece is stored (residual / blend operands: refused with PHASE)
                         const int ocol = oc(t);
                         const int c8o = (ocol - wcol0);
                         const f4 v0 = *(const f4*)(stg + prt * SLD + c8o), v1 = *(const f4*)(stg + prt * SLD + c8o + 4);
@@ -368,7 +382,7 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmArgs& e, f4 (&acc)[BM 
                             h8 pk;
 #pragma unroll
                             for (int i = 0; i < 8; ++i) pk[i] = (half_t)x[i];
-                            const unsigned o16 = (unsigned)row * (unsigned)e.ld16 + (unsigned)ocol;
+                            const unsigned o16 = (unsigned)orow * (unsigned)e.ld16 + (unsigned)ocol;
                             *(h8*)((half_t*)e.out16 + o16) = pk;
                             if (e.out16_lo_off) {      // split operand: the rounding residual rides along (hi + lo == x to ~2^-22)
                                 h8 lo;
@@ -388,7 +402,7 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmArgs& e, f4 (&acc)[BM 
                         const int sg_dt = in2 ? s2_dt : (in1 ? s1_dt : e.seg[0].dtype);
                         // 32-bit element offsets off the (scalar) bases: checked on the host (op_igemm: every row-major operand of the epilogue
                         // spans < 2^32 elements); 64-bit per-lane addresses cost the 80-wide wave tile its last registers
-                        const unsigned o = (unsigned)row * (unsigned)sg_ld + (unsigned)(ocol - sg_cb);
+                        const unsigned o = (unsigned)orow * (unsigned)sg_ld + (unsigned)(ocol - sg_cb);
                         if (sg_dt == DT_F16) {
                             h8 pk;
 #pragma unroll
@@ -436,13 +450,13 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmArgs& e, f4 (&acc)[BM 
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi) {
                 const int rbase = m0 + wm * WM + mi * 16 + erow;
-                if (rbase >= e.M) continue;
+                if (rbase >= Mrows) continue;
                 float v[4];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int row = rbase + i;
                     float x = acc[mi][ni][i] + bh;
-                    if (e.rowvec && row < e.M) x += e.rowvec[(size_t)(row / e.rows_per_img) * e.rowvec_ld + pcol];
+                    if (e.rowvec && row < Mrows) x += e.rowvec[(size_t)(row / rpi) * e.rowvec_ld + pcol];
                     if (e.geglu) {
                         const float g = acc[mi][ni + (NI > 1 ? 1 : 0)][i] + bg;
                         x = x * gelu_erf_f(g);
@@ -456,7 +470,7 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmArgs& e, f4 (&acc)[BM 
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const int row = rbase + i;
-                        if (row < e.M) store_from_f32(sg.out, (size_t)row * sg.ld + scol, sg.dtype, v[i]);
+                        if (row < Mrows) store_from_f32(sg.out, (size_t)out_row(row) * sg.ld + scol, sg.dtype, v[i]);
                     }
                 } else {
                     const int img = rbase / sg.L, tok = rbase - img * sg.L;

@@ -10,7 +10,9 @@
 // ------------------------------------------------------------------------------------------
 // Implicit GEMM (MFMA f16 -> f32):  out[m][n] = epilogue( sum_k Agather[m][k] * W[n][k] )
 // ------------------------------------------------------------------------------------------
-enum { IG_ROWS = 0, IG_CONV2D = 1, IG_TEMPORAL = 2 };
+// IG_CONV2D_PHASE: a 3x3 conv (padding 1) over a nearest x2 up-sampled map as four 2x2 convs over the source map, one per output
+// phase (oy & 1, ox & 1) -- taps = 4, up = 2, W = the phase pack of op_pack_conv_w_phase; see include/ctrl_hip.h: mode
+enum { IG_ROWS = 0, IG_CONV2D = 1, IG_TEMPORAL = 2, IG_CONV2D_PHASE = 3 };
 enum { SEG_ROW = 0, SEG_TRANSPOSED = 1 };
 
 typedef ctrl_igemm_seg IGemmSeg;     // see include/ctrl_hip.h for field docs
@@ -254,6 +256,10 @@ int op_pack_conv_w(const void* w, int dtype, half_t* out, int Cout, int Cin, int
 //   ovf (optional, device): set to 1 when a value does not fit fp16 (|w| > 65504, inf, nan)
 // split-operand form: fp16 [Cout][taps][2*Cin], the Cin weights of every tap twice
 int op_pack_conv_w_dup(const void* w, int dtype, half_t* out, int Cout, int Cin, int taps, hipStream_t s, int* ovf = nullptr);
+// phase form of a 3x3 conv over a nearest x2 up-sampled map (IG_CONV2D_PHASE): [Cout][Cin][3][3] -> fp16 [4 phases][Cout][4 taps][Cin];
+// phase (a, b) = (oy & 1, ox & 1), tap (ty, tx) = the sum of the 3x3 weights whose window row / column falls on source row
+// i + a - 1 + ty / column j + b - 1 + tx: rows {0} | {1, 2} for a = 0, {0, 1} | {2} for a = 1.  Summed in fp32, rounded once
+int op_pack_conv_w_phase(const void* w, int dtype, half_t* out, int Cout, int Cin, hipStream_t s, int* ovf = nullptr);
 // conv weight [Cout][Cin][3][3] -> fp32 [9][Cin][Cout] for the direct kernel
 int op_pack_conv_w_direct(const void* w, int dtype, float* out, int Cout, int Cin, hipStream_t s);
 // linear weight [N][K] -> fp16 [N][K]; optional GEGLU interleave of rows (N = 2*inner)

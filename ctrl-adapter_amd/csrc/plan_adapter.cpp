@@ -75,7 +75,10 @@ int build_block(ParamSink& ps, const std::string& pre, int C, const ctrl_adapter
         AdapterLayerW& L = b->layers[i];
         const std::string si = std::to_string(i);
         if (sr) {
-            TRY(build_resnet(ps, pre + ".spatial_resnets." + si, C, C, true, &L.sres));
+            // conv1 behind the x2 up-sampling gets its phase pack (four 2x2 convs, run_resnet) -- except in a block with outlier norm
+            // scales, which keeps the conservative selection throughout: there the 9-tap gather with its separately rounded weights
+            // stays (the SDXL chain with 1 % of the norm scales x 8 measures 1.04e-3 in the phase form against 0.90e-3)
+            TRY(build_resnet(ps, pre + ".spatial_resnets." + si, C, C, true, &L.sres, false, -1, up == 2 && i == 0 && !b->tok_f32));
             TRY(ps.linear(pre + ".spatial_resnets." + si + ".time_emb_proj", C, C, true, false, &L.sres_temb));
         }
         if (tr) {

@@ -6,10 +6,10 @@
 #include <cmath>
 
 // ------------------------------------------------------------------------------------------ builders
-int build_resnet(ParamSink& ps, const std::string& pre, int Cin, int Cout, bool force_shortcut, ResnetW* w, bool dup, int dup_shortcut) {
+int build_resnet(ParamSink& ps, const std::string& pre, int Cin, int Cout, bool force_shortcut, ResnetW* w, bool dup, int dup_shortcut, bool up2) {
     w->Cin = Cin; w->Cout = Cout;
     TRY(ps.norm(pre + ".norm1", Cin, &w->norm1));
-    TRY(ps.conv(pre + ".conv1", Cout, Cin, 3, false, &w->conv1, dup));
+    TRY(ps.conv(pre + ".conv1", Cout, Cin, 3, false, &w->conv1, dup, up2));
     // time_emb_proj is registered by the caller (batched across blocks) to keep state-dict order irrelevant
     TRY(ps.norm(pre + ".norm2", Cout, &w->norm2));
     TRY(ps.conv(pre + ".conv2", Cout, Cout, 3, false, &w->conv2, dup));
@@ -110,6 +110,12 @@ int run_conv(Ctx& cx, const ConvW& c, const half_t* x, const TV& y, int N, int H
     g.A = x; g.lda = o.lda ? o.lda : c.Cin; g.mode = as_rows ? IG_ROWS : IG_CONV2D; g.Cin = c.Cin; g.taps = c.taps;
     g.Hin = Hin; g.Win = Win; g.Hout = Hout; g.Wout = Wout; g.stride = o.stride; g.up = o.up; g.tap_origin = o.tap_origin;
     g.W = c.w; g.M = N * Hout * Wout; g.Nout = c.Cout; g.Ktot = c.taps * c.Cin;
+    if (o.phase) {
+        // the 3x3 window of an output pixel of a nearest x2 map touches a 2x2 block of source pixels: four 2x2 convs, 4/9 of the FLOPs
+        CTRL_CHECK(c.w_phase && c.taps == 9 && o.up == 2 && o.stride == 1 && !o.tap_origin && !c.dup && !o.res.ok(),
+                   "conv: the phase form needs a plain 3x3 conv with a phase pack behind an x2 up-sampling, without a residual");
+        g.mode = IG_CONV2D_PHASE; g.taps = 4; g.Ktot = 4 * c.Cin; g.W = c.w_phase;
+    }
     g.bias = c.b; g.rowvec = o.rowvec; g.rowvec_ld = o.rowvec_ld; g.rows_per_img = Hout * Wout;
     g.scale = 1.f; g.act = o.act; g.a_split = c.paired ? 2 : (c.dup ? 1 : 0);
     set_res(g, o.res, c.Cout);
@@ -143,6 +149,8 @@ int run_resnet(Ctx& cx, const ResnetW& w, const TV& x, const TV& out, int N, int
     // conv1 output feeds only GroupNorm: keep it in the stream dtype (its statistics are taken from this copy)
     TV h1 = cx.h1_f16 ? tv16(cx.h((size_t)N * Ho * Wo * w.Cout)) : stream_alloc(cx, (size_t)N * Ho * Wo * w.Cout, false);
     ConvOpts o1; o1.up = up; o1.rowvec = temb_proj; o1.rowvec_ld = temb_ld;
+    // (the policy is read here, per forward: CTRL_CONV_UP_PHASE=0 is the A/B switch and the fallback to the 9-tap gather)
+    o1.phase = up == 2 && w.conv1.w_phase != nullptr && !w.conv1.dup && !policy_is0(P_CONV_UP_PHASE);
     TRY(run_conv(cx, w.conv1, a, h1, N, H, W, o1));
     half_t* b = cx.h((size_t)N * Ho * Wo * w.conv2.Cin);
     TRY(run_groupnorm(cx, w.norm2, h1, b, N, Ho * Wo, eps, true, w.conv2.dup));

@@ -19,7 +19,8 @@ struct Lin { half_t* w = nullptr; float* b = nullptr; int N = 0, K = 0; bool geg
 // dup: split-operand convolution -- Cin is the K per tap the kernel walks (2 x the logical width: [hi | lo] halves of the
 // operand rows against the weights repeated twice), see ctrl_igemm_desc::a_split
 // paired: the split operand is walked in (hi, lo) pairs against the PLAIN weight pack (ctrl_igemm_desc::a_split == 2)
-struct ConvW { half_t* w = nullptr; float* b = nullptr; int Cout = 0, Cin = 0, taps = 0; bool dup = false, paired = false; };
+// w_phase: a 3x3 conv that runs behind a nearest x2 up-sampling, packed once more as four 2x2 phase convs (op_pack_conv_w_phase)
+struct ConvW { half_t* w = nullptr; float* b = nullptr; int Cout = 0, Cin = 0, taps = 0; bool dup = false, paired = false; half_t* w_phase = nullptr; };
 // w16: fp16 [Cout][9][Cin] copy for the MFMA form of the small convolutions (op_conv3x3_small_mfma), when the layer qualifies
 struct ConvD { float* w = nullptr; float* b = nullptr; int Cout = 0, Cin = 0; half_t* w16 = nullptr; };
 struct Norm { float* g = nullptr; float* b = nullptr; int C = 0; };
@@ -33,7 +34,8 @@ struct ParamSink {
     // several bias-free / biased linears with the same K concatenated along N (QKV, batched time projections)
     virtual int linear_cat(const std::vector<std::string>& names, const std::vector<int>& Ns, int K, bool bias, Lin* out) = 0;
     // nn.Conv2d(Cin, Cout, k) for the implicit GEMM: k = 1 | 3 ; nn.Conv3d (3,1,1) when temporal
-    virtual int conv(const std::string& name, int Cout, int Cin, int k, bool temporal, ConvW* out, bool dup = false) = 0;
+    // phase: also the phase pack (ConvW::w_phase) where the conv qualifies -- a plain 3x3 with Cin % 64 == 0
+    virtual int conv(const std::string& name, int Cout, int Cin, int k, bool temporal, ConvW* out, bool dup = false, bool phase = false) = 0;
     // nn.Conv2d(Cin, Cout, 3) for the direct small-channel kernel
     virtual int conv_direct(const std::string& name, int Cout, int Cin, ConvD* out) = 0;
     virtual int norm(const std::string& name, int C, Norm* out) = 0;
@@ -62,7 +64,7 @@ struct SpecCollector : ParamSink {
         for (size_t i = 0; i < names.size(); ++i) linear(names[i], Ns[i], K, bias, false, nullptr);
         return 0;
     }
-    int conv(const std::string& name, int Cout, int Cin, int k, bool temporal, ConvW*, bool) override {
+    int conv(const std::string& name, int Cout, int Cin, int k, bool temporal, ConvW*, bool, bool) override {
         if (temporal) entries.push_back({name + ".weight", {Cout, Cin, 3, 1, 1}});
         else entries.push_back({name + ".weight", {Cout, Cin, k, k}});
         entries.push_back({name + ".bias", {Cout}});
@@ -168,7 +170,7 @@ struct Packer : ParamSink {
         out->N = Ntot; out->K = K; out->geglu = false;
         return 0;
     }
-    int conv(const std::string& name, int Cout, int Cin, int k, bool temporal, ConvW* out, bool dup) override {
+    int conv(const std::string& name, int Cout, int Cin, int k, bool temporal, ConvW* out, bool dup, bool phase) override {
         const ctrl_tensor_ref* t;
         const int taps = temporal ? 3 : k * k;
         if (temporal) TRY(get(name + ".weight", {Cout, Cin, 3, 1, 1}, &t));
@@ -178,6 +180,12 @@ struct Packer : ParamSink {
         if (dup && !paired) TRY(op_pack_conv_w_dup(t->data, t->dtype, out->w, Cout, Cin, taps, s, ovf_flag()));
         else TRY(op_pack_conv_w(t->data, t->dtype, out->w, Cout, Cin, taps, s, ovf_flag()));
         out->paired = paired;
+        out->w_phase = nullptr;
+        if (phase && !dup && !temporal && k == 3 && Cin % 64 == 0) {
+            // from the weights as loaded: the tap sums are taken in fp32 and rounded to fp16 once
+            TRY(dalloc((size_t)16 * Cout * Cin * sizeof(half_t), (void**)&out->w_phase));
+            TRY(op_pack_conv_w_phase(t->data, t->dtype, out->w_phase, Cout, Cin, s, ovf_flag()));
+        }
         TRY(dalloc((size_t)Cout * sizeof(float), (void**)&out->b));
         TRY(vec(name + ".bias", Cout, false, out->b));
         out->Cout = Cout; out->Cin = dup ? 2 * Cin : Cin; out->taps = taps; out->dup = dup;
@@ -483,7 +491,9 @@ struct TemporalTBW {        // TemporalBasicTransformerBlock
 };
 
 // dup: split [hi | lo] operands for conv1 / conv2; dup_shortcut: the same for the 1x1 shortcut (-1 = as dup)
-int build_resnet(ParamSink& ps, const std::string& pre, int Cin, int Cout, bool force_shortcut, ResnetW* w, bool dup = false, int dup_shortcut = -1);
+// up2: the block runs behind a nearest x2 up-sampling (run_resnet with up = 2): conv1 also gets its phase pack
+int build_resnet(ParamSink& ps, const std::string& pre, int Cin, int Cout, bool force_shortcut, ResnetW* w, bool dup = false, int dup_shortcut = -1,
+                 bool up2 = false);
 int build_attn_self(ParamSink& ps, const std::string& pre, int dim, int heads, int D, AttnW* w);
 int build_attn_cross(ParamSink& ps, const std::string& pre, int dim, int cross, int heads, int D, AttnW* w);
 int build_basic_tb(ParamSink& ps, const std::string& pre, int dim, int heads, int D, int cross, BasicTBW* w);
@@ -569,6 +579,7 @@ struct ConvOpts {
     int res_up = 0;            // 2: res is the half-resolution map, read through a nearest x2 up-sampling (ctrl_igemm_desc::res_up)
     int act = 0;
     int tap_origin = 0;        // 1: a 3x3 conv whose taps start at stride*o -- Downsample2D(padding=0) (ctrl_igemm_desc::tap_origin)
+    bool phase = false;        // up == 2 on a 3x3 conv with a phase pack: four 2x2 convs over the source map (ctrl_igemm_desc::mode 3)
 };
 int run_conv(Ctx& cx, const ConvW& c, const half_t* x, const TV& y, int N, int Hin, int Win, const ConvOpts& o);
 // rowvec (optional): fp32 [M / rows_per_vec][rowvec_ld] added to every row of its group by the GEMM epilogue

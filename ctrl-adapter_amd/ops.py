@@ -9,7 +9,7 @@ import torch
 
 from . import _lib as L
 
-IG_ROWS, IG_CONV2D, IG_TEMPORAL = 0, 1, 2
+IG_ROWS, IG_CONV2D, IG_TEMPORAL, IG_CONV2D_PHASE = 0, 1, 2, 3
 SEG_ROW, SEG_TRANSPOSED = 0, 1
 
 
@@ -32,6 +32,16 @@ def pack_conv_w_dup(w):
     taps = w[0, 0].numel()
     out = _f16(cout, taps * 2 * cin)
     L.check(L.lib().ctrl_op_pack_conv_w_dup(L.ptr(w.contiguous()), L.dtype_code(w.dtype), L.ptr(out), cout, cin, taps, L.cur_stream()))
+    return out
+
+
+def pack_conv_w_phase(w):
+    """[Cout][Cin][3][3] -> fp16 [4][Cout][4*Cin]: the four 2x2 phase convs of a 3x3 conv over a nearest x2 up-sampled map
+    (include/ctrl_hip.h: ctrl_op_pack_conv_w_phase; the W operand of an IG_CONV2D_PHASE problem)"""
+    cout, cin = w.shape[0], w.shape[1]
+    assert tuple(w.shape[2:]) == (3, 3)
+    out = _f16(4, cout, 4 * cin, device=w.device)
+    L.check(L.lib().ctrl_op_pack_conv_w_phase(L.ptr(w.contiguous()), L.dtype_code(w.dtype), L.ptr(out), cout, cin, L.cur_stream()))
     return out
 
 
@@ -64,6 +74,13 @@ def igemm(A, lda, W, M, Nout, Cin, taps=1, mode=IG_ROWS, geom=None, bias=None, r
     splitk_tickets: zeroed int32 ticket words of the in-launch split-K reduction (None: the library zeroes its own)"""
     d = igemm_desc(**{k: v for k, v in locals().items() if k != "pinned"})
     L.check((L.lib().ctrl_op_igemm_pinned if pinned else L.lib().ctrl_op_igemm)(C.byref(d), L.cur_stream()))
+
+
+def igemm_group(descs):
+    """1..4 problems (igemm_desc) through ctrl_op_igemm_group: one launch when they agree in everything but their addresses, else one
+    launch each; the caller keeps the tensors behind the descriptors alive"""
+    arr = (L.IGemmDesc * len(descs))(*descs)
+    L.check(L.lib().ctrl_op_igemm_group(arr, len(descs), L.cur_stream()))
 
 
 def igemm_splitk_plan(d):

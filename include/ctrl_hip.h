@@ -71,9 +71,14 @@ typedef struct ctrl_igemm_seg {
 typedef struct ctrl_igemm_desc {
     const void* A;      /* fp16 activations, channels-last */
     int64_t lda;        /* elements between consecutive pixels/rows */
-    int32_t mode;       /* 0 rows (linear / 1x1), 1 conv2d, 2 temporal (3 frame taps) */
+    int32_t mode;       /* 0 rows (linear / 1x1), 1 conv2d, 2 temporal (3 frame taps), 3 conv2d in PHASE form: a 3x3 conv (padding 1)
+                           over a nearest x2 up-sampled map, computed as four 2x2 convs over the SOURCE map, one per output phase
+                           (oy & 1, ox & 1) -- 4/9 of the FLOPs.  taps = 4, up = 2, stride = 1, tap_origin = 0, Hin / Win = the source
+                           grid, Hout = 2 Hin, Wout = 2 Win, M = images * Hout * Wout, Ktot = 4 * Cin, W = the phase pack
+                           fp16 [4][Nout][4][Cin] of ctrl_op_pack_conv_w_phase.  Row-major outputs only; no residual, GEGLU, blend,
+                           split operand or split-K; Cin % 64 == 0 */
     int32_t Cin;        /* K per tap */
-    int32_t taps;       /* 1 | 9 | 3 */
+    int32_t taps;       /* 1 | 9 | 3 (temporal) | 4 (phase form) */
     int32_t Hin, Win, Hout, Wout, stride, up;   /* conv2d geometry; up = nearest up-sampling folded into the gather */
     int32_t F, HW;      /* temporal: frames per clip, rows per frame */
     int32_t t_pad;      /* temporal, frame-sharded clip: A = padded [clip][F+2][HW][lda] (slots 0 / F+1 = halo frames), M rows = the F local frames */
@@ -124,6 +129,9 @@ int ctrl_op_igemm(const ctrl_igemm_desc* d, void* stream);
 /* Test ABI.  The pinned form of the encoder plans: the 64 x 64 x 64 tile at every M, never split-K (row-major problems with
    Cin % 64 == 0 on the aligned vector epilogue; anything else is refused). */
 int ctrl_op_igemm_pinned(const ctrl_igemm_desc* d, void* stream);
+/* Test ABI.  n (1..4) problems as the plans launch the sibling adapter blocks of a pyramid level: ONE launch when the descriptors agree
+   in everything but their addresses (and grouped launches are on, ctrl_group_launches), one launch each otherwise. */
+int ctrl_op_igemm_group(const ctrl_igemm_desc* d, int n, void* stream);
 /* Test ABI.  What ctrl_op_igemm would do with the descriptor's split-K scratch: the number of K splits (1 = none; depends on the
    descriptor's pointers and strides and on ctrl_igemm_set_wide), and the exact sizes of the scratch (bytes) and of the zeroed
    ticket words (int32 words; 0 = the in-launch reduction does not apply) for that many splits. */
@@ -276,6 +284,10 @@ int ctrl_op_pack_conv_w(const void* w, int dtype, void* out, int Cout, int Cin, 
 /* weights of a split-operand convolution: [Cout][taps][2*Cin], every tap's Cin weights twice (for the hi and the lo half) */
 int ctrl_op_pack_conv_w_dup(const void* w, int dtype, void* out, int Cout, int Cin, int taps, void* stream);
 int ctrl_op_pack_conv_w_direct(const void* w, int dtype, float* out, int Cout, int Cin, void* stream);
+/* 3x3 conv weight [Cout][Cin][3][3] -> the phase pack fp16 [4][Cout][4][Cin] of ctrl_igemm_desc::mode 3: phase 2a + b, tap 2ty + tx =
+   the sum of w[..][ky][kx] over ky in S(a, ty), kx in S(b, tx), S(0,0) = {0}, S(0,1) = {1,2}, S(1,0) = {0,1}, S(1,1) = {2}; summed
+   in fp32 in (ky, kx) order, rounded to fp16 once */
+int ctrl_op_pack_conv_w_phase(const void* w, int dtype, void* out, int Cout, int Cin, void* stream);
 int ctrl_op_pack_linear_w(const void* w, int dtype, void* out, int N, int K, int geglu, void* stream);
 int ctrl_op_pack_vec(const void* v, int dtype, float* out, int N, int geglu, void* stream);
 
