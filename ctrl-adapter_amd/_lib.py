@@ -147,6 +147,8 @@ EXPORTS = [
     "ctrl_vae_encoder_forward", "ctrl_op_vae_row_softmax", "ctrl_op_vae_posterior",
     "ctrl_vae_decoder_param_count", "ctrl_vae_decoder_param_spec", "ctrl_vae_decoder_create", "ctrl_vae_decoder_destroy",
     "ctrl_vae_decoder_forward", "ctrl_vae_decoder_forward_strided", "ctrl_op_vae_dec_head", "ctrl_op_vae_dec_tail",
+    "ctrl_vae_tdecoder_param_count", "ctrl_vae_tdecoder_param_spec", "ctrl_vae_tdecoder_create", "ctrl_vae_tdecoder_destroy",
+    "ctrl_vae_tdecoder_forward", "ctrl_op_vae_time_conv",
 ]
 
 _lib = None
@@ -165,7 +167,8 @@ def lib():
         for name in EXPORTS:
             fn = getattr(_lib, name)
             if name not in ("ctrl_last_error", "ctrl_policy_get", "ctrl_policy_name", "ctrl_controlnet_destroy", "ctrl_adapter_destroy", "ctrl_rccl_comm_destroy", "ctrl_rccl_comm_bytes_sent",
-                            "ctrl_text_encoder_destroy", "ctrl_vision_encoder_destroy", "ctrl_vae_encoder_destroy", "ctrl_vae_decoder_destroy"):
+                            "ctrl_text_encoder_destroy", "ctrl_vision_encoder_destroy", "ctrl_vae_encoder_destroy", "ctrl_vae_decoder_destroy",
+                            "ctrl_vae_tdecoder_destroy"):
                 fn.restype = C.c_int
         _lib.ctrl_policy_get.restype = C.c_char_p
         _lib.ctrl_policy_get.argtypes = [C.c_char_p]
@@ -216,6 +219,12 @@ def lib():
                                               C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p]
         _lib.ctrl_op_vae_dec_tail.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int,
                                               C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        _lib.ctrl_vae_tdecoder_destroy.restype = None
+        _lib.ctrl_vae_tdecoder_destroy.argtypes = [C.c_void_p]
+        _lib.ctrl_vae_tdecoder_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
+                                                   C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        _lib.ctrl_op_vae_time_conv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                               C.c_int, C.c_void_p]
         _lib.ctrl_rccl_comm_destroy.restype = None
         _lib.ctrl_rccl_comm_destroy.argtypes = [C.c_void_p]
         _lib.ctrl_rccl_comm_bytes_sent.restype = C.c_int64

@@ -167,6 +167,11 @@ int op_vae_dec_head(const void* z, int dt, float scale, const float* wpq, const 
                     int lat, int h, int wd, long ch_stride, int Cout, hipStream_t s);
 int op_vae_dec_tail(const float* x, const float* stats, const float* gamma, const float* beta, float eps, const float* w, const float* b,
                     int H, int W, int C, int Cout, int kind, void* out, int out_dt, hipStream_t s);
+// Temporal decoder (vae.hip): time_conv_out over the frames of one clip.  x fp32 NCHW [F][Cout][H*W] (the tail kernel's SAMPLE / fp32
+// frames) -> Conv3d (3,1,1) with zero frames outside [0, F) (w fp32 [Cout][Cout][3] as the checkpoint holds it, b [Cout], Cout <= 4) in
+// fp32 -> the epilogue `kind` of the tail kernel over the F frames (NCHW [F][Cout][H][W], or NHWC bytes [F][H][W][Cout])
+int op_vae_time_conv(const float* x, const float* w, const float* b, int F, int H, int W, int Cout, int kind, void* out, int out_dt,
+                     hipStream_t s);
 
 // temporal attention over the frame axis: tokens X [(b*F+f)*HW + p][...]; seq = F (<= 32)
 typedef ctrl_tattn_desc TAttnArgs;

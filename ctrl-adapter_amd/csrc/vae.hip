@@ -10,6 +10,8 @@
 // and of the decoder half (AutoencoderKL.decode; csrc/plan_vae_decoder.cpp):
 //   vae_dec_head_kernel     latents * scale -> post_quant_conv -> conv_in, all fp32, NCHW latents of any dtype -> the fp32 NHWC stream
 //   vae_dec_tail_kernel     conv_norm_out + SiLU + conv_out + the output epilogue (sample / [0, 1] / uint8) in one pass over the stream
+// and of the temporal decoder (AutoencoderKLTemporalDecoder.decode; csrc/plan_vae_tdecoder.cpp):
+//   vae_time_conv_kernel    time_conv_out over the frames of a clip (the tail kernel's fp32 samples) + the same output epilogue
 // Each computes a row or a pixel on its own: an image's results do not depend on the batch it is in.
 #include "ops.h"
 #include <math.h>
@@ -247,7 +249,136 @@ __global__ void __launch_bounds__(256) vae_dec_tail_kernel(const float* __restri
     }
 }
 
+// time_conv_out of the temporal decoder (Conv3d (3,1,1), padding (1,0,0), OC -> OC) over the fp32 NCHW frames x [F][OC][HW] the tail
+// kernel wrote, + the output epilogue.  Memory-bound: a thread owns all OC channels of PV consecutive pixels (VEC: 4, one 16-byte load
+// per plane; consecutive lanes read consecutive 16 bytes) and walks kTcFrames frames with a three-frame window in registers, so a plane
+// is read once per walk (+ its two halo frames); the 3 * OC * OC weights are uniform (scalar loads).  Frames outside [0, F) are zero.
+constexpr int kTcFrames = 4;
+
+template <int OC, bool VEC>
+__global__ void __launch_bounds__(256) vae_time_conv_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                            const float* __restrict__ b, int F, long HW, int kind, void* __restrict__ out,
+                                                            int out_dt) {
+    constexpr int PV = VEC ? 4 : 1;
+    const size_t p0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * PV;
+    if (p0 >= (size_t)HW) return;
+    const int f0 = blockIdx.y * kTcFrames, f1 = min(F, f0 + kTcFrames);
+    float win[3][OC][PV];                          // frames f - 1, f, f + 1
+    auto load = [&](int f, float (&dst)[OC][PV]) {
+#pragma unroll
+        for (int c = 0; c < OC; ++c) {
+            if (f < 0 || f >= F) {
+#pragma unroll
+                for (int j = 0; j < PV; ++j) dst[c][j] = 0.f;
+            } else {
+                const float* p = x + ((size_t)f * OC + c) * (size_t)HW + p0;
+                if (VEC) {
+                    const f4 v = *(const f4*)p;
+#pragma unroll
+                    for (int j = 0; j < PV; ++j) dst[c][j] = v[j];
+                } else {
+                    dst[c][0] = *p;
+                }
+            }
+        }
+    };
+    load(f0 - 1, win[0]);
+    load(f0, win[1]);
+    for (int f = f0; f < f1; ++f) {
+        load(f + 1, win[2]);
+        float y[OC][PV];
+#pragma unroll
+        for (int o = 0; o < OC; ++o) {
+#pragma unroll
+            for (int j = 0; j < PV; ++j) {
+                float acc = b[o];
+#pragma unroll
+                for (int c = 0; c < OC; ++c)
+#pragma unroll
+                    for (int t = 0; t < 3; ++t) acc = fmaf(w[(o * OC + c) * 3 + t], win[t][c][j], acc);
+                y[o][j] = round_to_dt(acc, out_dt);       // what .sample holds in the module's dtype
+            }
+        }
+        if (kind == CTRL_VAE_DEC_U8) {
+            // NHWC bytes: the thread's PV pixels x OC channels are PV * OC consecutive bytes (VEC: OC aligned 32-bit words)
+            unsigned char q[PV * OC];
+#pragma unroll
+            for (int j = 0; j < PV; ++j)
+#pragma unroll
+                for (int o = 0; o < OC; ++o)
+                    q[j * OC + o] = (unsigned char)rintf(fminf(fmaxf(y[o][j] * 0.5f + 0.5f, 0.f), 1.f) * 255.0f);      // ties to even
+            unsigned char* op = (unsigned char*)out + ((size_t)f * (size_t)HW + p0) * OC;
+            if (VEC) {
+#pragma unroll
+                for (int k = 0; k < OC; ++k)
+                    ((unsigned*)op)[k] = (unsigned)q[4 * k] | ((unsigned)q[4 * k + 1] << 8) | ((unsigned)q[4 * k + 2] << 16) | ((unsigned)q[4 * k + 3] << 24);
+            } else {
+#pragma unroll
+                for (int o = 0; o < OC; ++o) op[o] = q[o];
+            }
+        } else {
+            const bool unit = kind == CTRL_VAE_DEC_UNIT;
+#pragma unroll
+            for (int o = 0; o < OC; ++o) {
+                const size_t i = ((size_t)f * OC + o) * (size_t)HW + p0;
+                float v[PV];
+#pragma unroll
+                for (int j = 0; j < PV; ++j) v[j] = unit ? fminf(fmaxf(y[o][j] * 0.5f + 0.5f, 0.f), 1.f) : y[o][j];
+                if (!VEC) {
+                    if (unit) ((float*)out)[i] = v[0];
+                    else store_from_f32(out, i, out_dt, v[0]);
+                } else if (unit || out_dt == DT_F32) {
+                    *(f4*)((float*)out + i) = f4{v[0], v[1], v[2], v[3]};
+                } else if (out_dt == DT_F16) {
+                    *(h4*)((half_t*)out + i) = h4{(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
+                } else {
+                    typedef u16 us4 __attribute__((ext_vector_type(4)));
+                    *(us4*)((u16*)out + i) = us4{f32_to_bf16(v[0]), f32_to_bf16(v[1]), f32_to_bf16(v[2]), f32_to_bf16(v[3])};
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < OC; ++c)
+#pragma unroll
+            for (int j = 0; j < PV; ++j) { win[0][c][j] = win[1][c][j]; win[1][c][j] = win[2][c][j]; }
+    }
+}
+
+template <int OC>
+int launch_time_conv(bool vec, dim3 grid, hipStream_t s, const float* x, const float* w, const float* b, int F, long HW, int kind, void* out,
+                     int out_dt) {
+    if (vec) LAUNCH("vae_time_conv", (vae_time_conv_kernel<OC, true>), grid, dim3(256), 0, s, x, w, b, F, HW, kind, out, out_dt);
+    else LAUNCH("vae_time_conv", (vae_time_conv_kernel<OC, false>), grid, dim3(256), 0, s, x, w, b, F, HW, kind, out, out_dt);
+    return 0;
+}
+
 }  // namespace
+
+int op_vae_time_conv(const float* x, const float* w, const float* b, int F, int H, int W, int Cout, int kind, void* out, int out_dt,
+                     hipStream_t s) {
+    CTRL_CHECK(x && w && b && out, "vae_time_conv: null argument");
+    CTRL_CHECK(F >= 1 && H >= 1 && W >= 1 && Cout >= 1 && Cout <= 4, "vae_time_conv: bad shape (1 <= channels <= 4)");
+    CTRL_CHECK(kind == CTRL_VAE_DEC_SAMPLE || kind == CTRL_VAE_DEC_UNIT || kind == CTRL_VAE_DEC_U8,
+               "vae_time_conv: kind must be 0 sample, 1 unit or 2 u8");
+    CTRL_CHECK(out_dt >= DT_F32 && out_dt <= DT_BF16, "vae_time_conv: bad dtype");
+    const long HW = (long)H * W;
+    // 16-byte loads and the packed stores need whole groups of 4 pixels per plane and aligned bases
+    // (4 output pixels are 16 bytes of fp32, 8 of fp16 / bf16, or Cout 32-bit words of NHWC bytes)
+    const uintptr_t oalign = kind == CTRL_VAE_DEC_U8 ? 3 : ((kind == CTRL_VAE_DEC_UNIT || out_dt == DT_F32) ? 15 : 7);
+    const bool vec = HW % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)out & oalign) == 0;
+    const long threads = vec ? HW / 4 : HW;
+    const long gx = (threads + 255) / 256, gy = (F + kTcFrames - 1) / kTcFrames;
+    CTRL_CHECK(gx < (1L << 31) && gy <= 65535, "vae_time_conv: too large");
+    const dim3 grid((unsigned)gx, (unsigned)gy);
+    const double osz = kind == CTRL_VAE_DEC_SAMPLE ? (out_dt == DT_F32 ? 4.0 : 2.0) : (kind == CTRL_VAE_DEC_UNIT ? 4.0 : 1.0);
+    PROF_WORK(2.0 * 3 * Cout * Cout * F * (double)HW, (double)F * HW * Cout * (4.0 + osz));
+    switch (Cout) {
+        case 1: return launch_time_conv<1>(vec, grid, s, x, w, b, F, HW, kind, out, out_dt);
+        case 2: return launch_time_conv<2>(vec, grid, s, x, w, b, F, HW, kind, out, out_dt);
+        case 3: return launch_time_conv<3>(vec, grid, s, x, w, b, F, HW, kind, out, out_dt);
+        default: return launch_time_conv<4>(vec, grid, s, x, w, b, F, HW, kind, out, out_dt);
+    }
+}
 
 int op_vae_row_softmax(const float* S, long lds, half_t* P, long ldp, int rows, int L, int Lpad, hipStream_t s) {
     CTRL_CHECK(S && P, "vae_row_softmax: null argument");

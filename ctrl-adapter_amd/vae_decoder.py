@@ -9,7 +9,7 @@ over one set of parameters), a drop-in for `pipe.vae`; and the two pipelines' de
 
 State-dict keys are diffusers' (`post_quant_conv.weight`, `decoder.conv_in.weight`, ...); a full VAE checkpoint loads into the decoder
 (encoder.* and quant_conv.* are ignored), and so do the legacy attention names (query / key / value / proj_attn).  SVD's
-AutoencoderKLTemporalDecoder is not covered."""
+AutoencoderKLTemporalDecoder is vae_temporal_decoder.py's: these classes refuse its checkpoint."""
 import torch
 
 from . import _lib as L
@@ -34,9 +34,9 @@ class DecoderOutput(tuple):
         return self
 
 
-def _run_decoder(m, plan, z, kind, scale, out_dtype, out=None):
-    """one ctrl_vae_decoder_forward of the module `m` (its device, dtype, latent_channels, up_factor) with the plan `plan`; `out`: a
-    contiguous tensor of the result's shape and dtype to write into (a slice of a larger buffer) instead of a new one"""
+def _decoder_io(m, z, kind, out_dtype, out):
+    """what every decoder forward of the module `m` (its device, dtype, latent_channels, up_factor) checks and prepares: (device, the
+    latents as the head kernel can read them, the output tensor of `kind`, the dtype `sample` is rounded to)"""
     dev = _check_gpu_input(m, z, "the latents", "live")
     if z.dim() != 4 or z.shape[1] != m.latent_channels:
         raise ValueError("the latents must be [N, %d, h, w] (got %s)" % (m.latent_channels, tuple(z.shape)))
@@ -55,10 +55,18 @@ def _run_decoder(m, plan, z, kind, scale, out_dtype, out=None):
         out = torch.empty(shape, dtype=odt, device=dev)
     elif tuple(out.shape) != shape or out.dtype != odt or out.device != dev or not out.is_contiguous():
         raise ValueError("out must be a contiguous %s tensor of shape %s on %s" % (odt, shape, dev))
+    if N and (z.stride(3) != 1 or z.stride(2) != w or z.stride(1) < h * w):      # the head kernel reads dense [h][w] planes at any two strides
+        z = z.contiguous()
+    return dev, z, out, dt
+
+
+def _run_decoder(m, plan, z, kind, scale, out_dtype, out=None):
+    """one ctrl_vae_decoder_forward of the module `m` with the plan `plan`; `out`: a contiguous tensor of the result's shape and dtype to
+    write into (a slice of a larger buffer) instead of a new one"""
+    dev, z, out, dt = _decoder_io(m, z, kind, out_dtype, out)
+    N, _, h, w = z.shape
     if N == 0:
         return out
-    if z.stride(3) != 1 or z.stride(2) != w or z.stride(1) < h * w:      # the head kernel reads dense [h][w] planes at any two strides
-        z = z.contiguous()
     with torch.cuda.device(dev):
         L.check(L.lib().ctrl_vae_decoder_forward_strided(plan(), L.ptr(z), L.dtype_code(z.dtype), N, h, w, z.stride(0), z.stride(1),
                                                          float(scale), int(kind), L.ptr(out), L.dtype_code(dt), L.cur_stream()))

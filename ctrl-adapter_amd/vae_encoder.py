@@ -151,7 +151,8 @@ class AutoencoderKLOutput(tuple):
 
 
 class AutoencoderKLEncoder(ParamTreeModule):
-    """The encoder of diffusers' AutoencoderKL / AutoencoderKLTemporalDecoder (their config kwargs; the decoder is not built).  An
+    """The encoder of diffusers' AutoencoderKL / AutoencoderKLTemporalDecoder (their config kwargs; the decoders are vae_decoder.py's and
+    vae_temporal_decoder.py's).  An
     image's latents are bit-identical alone or inside any batch."""
 
     _CREATE, _DESTROY = "ctrl_vae_encoder_create", "ctrl_vae_encoder_destroy"

@@ -692,6 +692,33 @@ int ctrl_op_vae_dec_head(const void* z, int z_dtype, float scale, const float* w
 int ctrl_op_vae_dec_tail(const float* x, const float* stats, const float* gamma, const float* beta, float eps, const float* w_out,
                          const float* b_out, int H, int W, int C, int Cout, int kind, void* out, int out_dtype, void* stream);
 
+/* ---- Temporal KL-VAE decoder (diffusers AutoencoderKLTemporalDecoder.decode: the TemporalDecoder behind SVD's decode_latents).  The
+ * config is the KL-VAE decoder's; there is no post_quant_conv. ---- */
+typedef struct ctrl_vae_tdecoder ctrl_vae_tdecoder;   /* opaque */
+/* parameters: diffusers' keys (decoder.conv_in.*, decoder.mid_block.resnets.{j}.{spatial_res_block,temporal_res_block}.*,
+   decoder.mid_block.resnets.{j}.time_mixer.mix_factor, decoder.mid_block.attentions.0.*, decoder.up_blocks.{i}.resnets.{j}.* likewise,
+   decoder.up_blocks.{i}.upsamplers.0.conv.*, decoder.conv_norm_out.*, decoder.conv_out.*, decoder.time_conv_out.*) */
+int ctrl_vae_tdecoder_param_count(const ctrl_vae_decoder_config* cfg);
+int ctrl_vae_tdecoder_param_spec(const ctrl_vae_decoder_config* cfg, int i, char* name, int name_len, int64_t shape[6], int* ndim);
+int ctrl_vae_tdecoder_create(const ctrl_vae_decoder_config* cfg, const ctrl_tensor_ref* tensors, int n_tensors, void* stream,
+                             ctrl_vae_tdecoder** out);
+void ctrl_vae_tdecoder_destroy(ctrl_vae_tdecoder* h);
+/* latents: `clips` clips of `num_frames` frames, frame (b, f) = image b * num_frames + f of the strided layout of
+   ctrl_vae_decoder_forward_strided ([latent_channels][h][w] planes channel_stride apart, images image_stride apart), multiplied by
+   `scale` on load; out: the clips' frames in the same order, the epilogue `kind` (CTRL_VAE_DEC_*) per frame.  Clips are decoded one
+   after the other (a clip's pixels are bit-identical whatever else is in the call); inside a clip the launches run over groups of
+   consecutive frames: frames_per_launch = 0 takes the largest group whose operands stay below 2^31 elements, a positive value caps
+   it (the result is the same up to the GEMM tiles' summation order).  The first forward of a larger (size, frames) allocates the
+   workspace (not under stream capture); every later one is capturable. */
+int ctrl_vae_tdecoder_forward(ctrl_vae_tdecoder* h, const void* latents, int latent_dtype, int clips, int num_frames, int lat_h, int lat_w,
+                              int64_t image_stride, int64_t channel_stride, float scale, int kind, void* out, int out_dtype,
+                              int frames_per_launch, void* stream);
+/* op level (csrc/vae.hip): time_conv_out of one clip.  x fp32 NCHW [F][Cout][H][W] (ctrl_op_vae_dec_tail's SAMPLE / fp32 frames) ->
+   Conv3d (3,1,1), zero frames outside [0, F) (w fp32 [Cout][Cout][3], b [Cout], Cout <= 4), fp32 -> the epilogue `kind` over the F
+   frames. */
+int ctrl_op_vae_time_conv(const float* x, const float* w, const float* b, int F, int H, int W, int Cout, int kind, void* out,
+                          int out_dtype, void* stream);
+
 /* ---- Router (model/ctrl_router.py) ---- */
 /* weights_out fp32 device [num_routers + (has_mid?1:0)][E]; wg fp32 device same shape (Linear(1,E).weight[:,0]
  * per router; ignored for equal_weights); mask host int[E] (NULL = all ones). */
