@@ -12,3 +12,4 @@ from .vision_encoder import CLIPVisionModelWithProjection, CLIPVisionModelOutput
 from .vae_encoder import AutoencoderKLEncoder, encode_svd_image_latents, prepare_i2vgen_image_latents  # noqa: F401
 from .vae_decoder import AutoencoderKL, AutoencoderKLDecoder, DecoderOutput, decode_i2vgen_latents, decode_sdxl_latents  # noqa: F401
 from .vae_temporal_decoder import AutoencoderKLTemporalDecoder, decode_svd_latents  # noqa: F401
+from .unet_spatio_temporal import UNetSpatioTemporalConditionModel, UNetSpatioTemporalConditionOutput  # noqa: F401

@@ -42,7 +42,7 @@ template <typename P> __device__ __forceinline__ P pick4(const Ptr4<P>& q, int z
 
 template <typename T>
 __global__ __launch_bounds__(256) void gn_stats_kernel(Ptr4<const T*> xs, Ptr4<float*> statss,
-                                                       int rows, int C, int G, int rows_per_block) {
+                                                       int rows, int C, int G, int rows_per_block, long ldx) {
     extern __shared__ float sh[];   // [rpi][2*C]: per (row lane, channel) sum | sumsq
     __shared__ int is_last;
     const T* __restrict__ x = pick4(xs, blockIdx.z);
@@ -58,13 +58,13 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(Ptr4<const T*> xs, Ptr4<f
 #pragma unroll
     for (int j = 0; j < 8; ++j) { s[j] = 0.f; ss[j] = 0.f; }
     if (tr < rpi) {
-        const T* xp = x + ((size_t)img * rows) * C + tc * 8;
+        const T* xp = x + ((size_t)img * rows) * ldx + tc * 8;      // (ldx: elements between the rows of x, C unless x is a column range)
         constexpr int U = sizeof(T) == 2 ? 8 : 4;       // loads in flight per thread
         int r = r0 + tr;
         for (; r + (U - 1) * rpi < r1; r += U * rpi) {
             float v[U][8];
 #pragma unroll
-            for (int u = 0; u < U; ++u) load8<T>(xp + (size_t)(r + u * rpi) * C, v[u]);
+            for (int u = 0; u < U; ++u) load8<T>(xp + (size_t)(r + u * rpi) * ldx, v[u]);
 #pragma unroll
             for (int u = 0; u < U; ++u)
 #pragma unroll
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(Ptr4<const T*> xs, Ptr4<f
         }
         for (; r < r1; r += rpi) {
             float v[8];
-            load8<T>(xp + (size_t)r * C, v);
+            load8<T>(xp + (size_t)r * ldx, v);
 #pragma unroll
             for (int j = 0; j < 8; ++j) { const float f = v[j]; s[j] += f; ss[j] += f * f; }
         }
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(Ptr4<const T*> xs, Ptr4<c
                                                        Ptr4<const float*> gammas, Ptr4<const float*> betas,
                                                        Ptr4<half_t*> ys, int rows, int C, int G, float eps,
                                                        int silu, int rows_per_block, long ldy, int lo_off,
-                                                       float stat_rows, long y_img_rows, long y_row0) {
+                                                       float stat_rows, long y_img_rows, long y_row0, long ldx) {
     const T* __restrict__ x = pick4(xs, blockIdx.z);
     const float* __restrict__ stats = pick4(statss, blockIdx.z);
     const float* __restrict__ gamma = pick4(gammas, blockIdx.z);
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(Ptr4<const T*> xs, Ptr4<c
         sc[j] = rstd * gamma[c];
         sf[j] = beta[c] - mean * sc[j];
     }
-    const T* xp = x + ((size_t)img * rows) * C + tc * 8;
+    const T* xp = x + ((size_t)img * rows) * ldx + tc * 8;
     half_t* yp = y + ((size_t)img * y_img_rows + y_row0) * ldy + tc * 8;
     // split operand (lo_off > 0): the row also carries lo = fp16(f - hi), so that hi + lo == f to ~2^-22
     auto emit = [&](const float (&v)[8], half_t* dst) {
@@ -201,13 +201,13 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(Ptr4<const T*> xs, Ptr4<c
     for (; r + 3 * rpi < r1; r += 4 * rpi) {
         float v[4][8];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) load8<T>(xp + (size_t)(r + u * rpi) * C, v[u]);
+        for (int u = 0; u < 4; ++u) load8<T>(xp + (size_t)(r + u * rpi) * ldx, v[u]);
 #pragma unroll
         for (int u = 0; u < 4; ++u) emit(v[u], yp + (size_t)(r + u * rpi) * ldy);
     }
     for (; r < r1; r += rpi) {
         float v[8];
-        load8<T>(xp + (size_t)r * C, v);
+        load8<T>(xp + (size_t)r * ldx, v);
         emit(v, yp + (size_t)r * ldy);
     }
 }
@@ -404,7 +404,7 @@ static int gn_rows_per_block(int imgs, int rows_per_img, int C, int target_block
 }
 
 size_t op_gn_stats_floats(int imgs, int rows_per_img, int C, int G) {
-    if (imgs < 1 || rows_per_img < 1 || C < 8 || G < 1) return 0;
+    if (imgs < 1 || rows_per_img < 1 || C < 8 || C / 8 > 256 || G < 1) return 0;
     const int rows_per_block = gn_rows_per_block(imgs, rows_per_img, C, 768);
     const int chunks = (rows_per_img + rows_per_block - 1) / rows_per_block;
     return (size_t)imgs * G * 2 + imgs + (chunks > 1 ? (size_t)imgs * chunks * G * 2 : 0);
@@ -417,8 +417,8 @@ template <typename P, typename A, typename F> static Ptr4<P> ptrs_of(const A* a,
 }
 static int pk16(const void* p) { return p ? 1 + (int)((uintptr_t)p & 15) : 0; }
 
-int op_gn_stats(const void* x, int x_dtype, float* stats, int imgs, int rows_per_img, int C, int G, hipStream_t s) {
-    const GnStatsArgs a = {x, x_dtype, stats, imgs, rows_per_img, C, G};
+int op_gn_stats(const void* x, int x_dtype, float* stats, int imgs, int rows_per_img, int C, int G, hipStream_t s, long ldx) {
+    const GnStatsArgs a = {x, x_dtype, stats, imgs, rows_per_img, C, G, ldx};
     if (t_collect) {
         int rc = 0;
         const int i = t_collect->slot(OpCollector::GN_STATS, s, &rc);
@@ -433,7 +433,7 @@ int op_gn_stats_group(const GnStatsArgs* a, int n, hipStream_t s) {
     CTRL_CHECK(a && n >= 1 && n <= kMaxGroup, "gn_stats_group: 1..4 problems");
     bool same = group_launches_enabled();
     for (int i = 1; i < n; ++i)
-        same = same && a[i].x_dtype == a[0].x_dtype && a[i].imgs == a[0].imgs && a[i].rows_per_img == a[0].rows_per_img && a[i].C == a[0].C && a[i].G == a[0].G;
+        same = same && a[i].x_dtype == a[0].x_dtype && a[i].imgs == a[0].imgs && a[i].rows_per_img == a[0].rows_per_img && a[i].C == a[0].C && a[i].G == a[0].G && a[i].ldx == a[0].ldx;
     if (n > 1 && !same) {
         for (int i = 0; i < n; ++i) TRY(op_gn_stats_group(a + i, 1, s));
         return 0;
@@ -442,6 +442,8 @@ int op_gn_stats_group(const GnStatsArgs* a, int n, hipStream_t s) {
     CTRL_CHECK(x_dtype == DT_F16 || x_dtype == DT_F32, "gn_stats: input must be fp16 or fp32");
     CTRL_CHECK(C % 8 == 0 && C % G == 0 && C / 8 <= 256, "gn_stats: C must be a multiple of 8 and of G, <= 2048");
     CTRL_CHECK(G <= 32, "gn_stats: at most 32 groups");
+    const long ldx = a[0].ldx > 0 ? a[0].ldx : C;
+    CTRL_CHECK(ldx >= C && ldx % 8 == 0, "gn_stats: the row stride of x must be a multiple of 8, at least C");
     // fewer, fatter workgroups than the apply pass: the last workgroup of an image adds all its chunks serially
     const int rows_per_block = gn_rows_per_block(imgs, rows_per_img, C, 768);
     const int chunks = (rows_per_img + rows_per_block - 1) / rows_per_block;
@@ -451,17 +453,17 @@ int op_gn_stats_group(const GnStatsArgs* a, int n, hipStream_t s) {
     const auto st = ptrs_of<float*>(a, n, [](const GnStatsArgs& q) { return q.stats; });
     if (x_dtype == DT_F32)
         LAUNCH("gn_stats", gn_stats_kernel<float>, dim3(chunks, imgs, n), dim3(256), lds, s,
-               ptrs_of<const float*>(a, n, [](const GnStatsArgs& q) { return q.x; }), st, rows_per_img, C, G, rows_per_block);
+               ptrs_of<const float*>(a, n, [](const GnStatsArgs& q) { return q.x; }), st, rows_per_img, C, G, rows_per_block, ldx);
     else
         LAUNCH("gn_stats", gn_stats_kernel<half_t>, dim3(chunks, imgs, n), dim3(256), lds, s,
-               ptrs_of<const half_t*>(a, n, [](const GnStatsArgs& q) { return q.x; }), st, rows_per_img, C, G, rows_per_block);
+               ptrs_of<const half_t*>(a, n, [](const GnStatsArgs& q) { return q.x; }), st, rows_per_img, C, G, rows_per_block, ldx);
     return 0;
 }
 
 int op_gn_apply(const void* x, int x_dtype, const float* stats, const float* gamma, const float* beta, half_t* y,
                 int imgs, int rows_per_img, int C, int G, float eps, int silu, hipStream_t s, long ldy, int lo_off,
-                long stat_rows, long y_img_rows, long y_row0) {
-    const GnApplyArgs a = {x, x_dtype, stats, gamma, beta, y, imgs, rows_per_img, C, G, eps, silu, ldy, lo_off, stat_rows, y_img_rows, y_row0};
+                long stat_rows, long y_img_rows, long y_row0, long ldx) {
+    const GnApplyArgs a = {x, x_dtype, stats, gamma, beta, y, imgs, rows_per_img, C, G, eps, silu, ldy, lo_off, stat_rows, y_img_rows, y_row0, ldx};
     if (t_collect) {
         int rc = 0;
         const int i = t_collect->slot(OpCollector::GN_APPLY, s, &rc);
@@ -478,7 +480,7 @@ int op_gn_apply_group(const GnApplyArgs* a, int n, hipStream_t s) {
     for (int i = 1; i < n; ++i)
         same = same && a[i].x_dtype == a[0].x_dtype && a[i].imgs == a[0].imgs && a[i].rows_per_img == a[0].rows_per_img && a[i].C == a[0].C &&
                a[i].G == a[0].G && a[i].eps == a[0].eps && a[i].silu == a[0].silu && a[i].ldy == a[0].ldy && a[i].lo_off == a[0].lo_off &&
-               a[i].stat_rows == a[0].stat_rows && a[i].y_img_rows == a[0].y_img_rows && a[i].y_row0 == a[0].y_row0;
+               a[i].stat_rows == a[0].stat_rows && a[i].y_img_rows == a[0].y_img_rows && a[i].y_row0 == a[0].y_row0 && a[i].ldx == a[0].ldx;
     if (n > 1 && !same) {
         for (int i = 0; i < n; ++i) TRY(op_gn_apply_group(a + i, 1, s));
         return 0;
@@ -488,6 +490,8 @@ int op_gn_apply_group(const GnApplyArgs* a, int n, hipStream_t s) {
     const long y_row0 = a[0].y_row0;
     CTRL_CHECK(C % 8 == 0 && C % G == 0 && C / 8 <= 256, "gn_apply: C must be a multiple of 8 and of G, <= 2048");
     if (ldy == 0) ldy = C;
+    const long ldx = a[0].ldx > 0 ? a[0].ldx : C;
+    CTRL_CHECK(ldx >= C && ldx % 8 == 0, "gn_apply: the row stride of x must be a multiple of 8, at least C");
     if (stat_rows <= 0) stat_rows = rows_per_img;
     if (y_img_rows <= 0) y_img_rows = rows_per_img;
     CTRL_CHECK(y_row0 >= 0 && y_row0 + rows_per_img <= y_img_rows, "gn_apply: bad output image layout");
@@ -504,11 +508,11 @@ int op_gn_apply_group(const GnApplyArgs* a, int n, hipStream_t s) {
     if (x_dtype == DT_F32)
         LAUNCH("gn_apply", gn_apply_kernel<float>, dim3(chunks, imgs, n), dim3(256), 0, s,
                ptrs_of<const float*>(a, n, [](const GnApplyArgs& q) { return q.x; }), st, ga, be, ys, rows_per_img, C, G, a[0].eps, a[0].silu,
-               rows_per_block, ldy, lo_off, (float)stat_rows, y_img_rows, y_row0);
+               rows_per_block, ldy, lo_off, (float)stat_rows, y_img_rows, y_row0, ldx);
     else
         LAUNCH("gn_apply", gn_apply_kernel<half_t>, dim3(chunks, imgs, n), dim3(256), 0, s,
                ptrs_of<const half_t*>(a, n, [](const GnApplyArgs& q) { return q.x; }), st, ga, be, ys, rows_per_img, C, G, a[0].eps, a[0].silu,
-               rows_per_block, ldy, lo_off, (float)stat_rows, y_img_rows, y_row0);
+               rows_per_block, ldy, lo_off, (float)stat_rows, y_img_rows, y_row0, ldx);
     return 0;
 }
 

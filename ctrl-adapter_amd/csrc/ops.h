@@ -184,13 +184,14 @@ int op_temporal_attn(const TAttnArgs& a, hipStream_t s);
 // `stats` holds op_gn_stats_floats(...) floats (results first, then tickets and per-workgroup partials) and must have
 // been zeroed once (the kernel leaves its tickets zero again).
 size_t op_gn_stats_floats(int imgs, int rows_per_img, int C, int G);
-int op_gn_stats(const void* x, int x_dtype, float* stats, int imgs, int rows_per_img, int C, int G, hipStream_t s);
+// ldx: elements between the rows of x (0 = C; larger: x is a column range of wider rows)
+int op_gn_stats(const void* x, int x_dtype, float* stats, int imgs, int rows_per_img, int C, int G, hipStream_t s, long ldx = 0);
 // y = (x-mean)*rstd*gamma+beta (optionally SiLU); x,y [imgs*rows][C]
 // ldy / lo_off: row stride of y (0 = C) and, when > 0, the column offset of the LOW half of a split operand
 // (y[r][c] = hi = fp16(v), y[r][lo_off + c] = fp16(v - hi)): consumed by a convolution packed with dup weights
 int op_gn_apply(const void* x, int x_dtype, const float* stats, const float* gamma, const float* beta, half_t* y,
                 int imgs, int rows_per_img, int C, int G, float eps, int silu, hipStream_t s, long ldy = 0, int lo_off = 0,
-                long stat_rows = 0, long y_img_rows = 0, long y_row0 = 0);
+                long stat_rows = 0, long y_img_rows = 0, long y_row0 = 0, long ldx = 0);
 //   stat_rows: rows per image the statistics in `stats` span (0 = rows_per_img; larger when a clip's frames are sharded
 //   over ranks and the sums were all-reduced); y_img_rows / y_row0: image i of y starts at row i*y_img_rows + y_row0
 //   (0 = dense): the padded operand layout of the frame-sharded temporal convolution
@@ -249,6 +250,10 @@ int op_router_softmax(const float* wg, const int* mask, float* out, int R, int E
 int op_conv3x3_direct(const void* in, int in_dtype, int in_nchw, const float* w, const float* bias, half_t* out,
                       int N, int Cin, int Cout, int Hin, int Win, int stride, int silu, hipStream_t s);
 
+// the SVD UNet's stem (Cin = 8): NCHW sample of any dtype -> fp32 NHWC rows (the residual stream), stride 1, no activation
+int op_conv3x3_direct_f32(const void* in, int in_dtype, const float* w, const float* bias, float* out, int N, int Cin, int Cout, int H,
+                          int W, hipStream_t s);
+
 // The same convolution on the matrix cores for the channels-last layers with Cin, Cout in {16, 32} (the conditioning embedder's
 // 16 -> 16, 16 -> 32 s2, 32 -> 32): x NHWC fp16, w fp16 [Cout][9][Cin] (op_pack_conv_w), out NHWC fp16 (+ bias, optional SiLU)
 bool op_conv3x3_small_mfma_applies(int Cin, int Cout);
@@ -273,6 +278,19 @@ int op_pack_linear_w(const void* w, int dtype, half_t* out, int N, int K, int ge
 int op_pack_vec(const void* v, int dtype, float* out, int N, int geglu, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
+// SVD backbone UNet (unet.hip)
+// ------------------------------------------------------------------------------------------
+// one skip tensor of the up path: out[r][col + c] = skip[r][c] (+ res(b, f, c, p)) for the B * F * HW rows r = (b F + f) HW + p and
+// c < C2, the fp32 master (row stride ld_out) and, when out16 is given, its fp16 mirror with one rounding.  res (optional): the adapter's
+// residual as the caller holds it, (b f) c h w (res_5d = 0) or b c f h w (res_5d = 1), fp32 / fp16 / bf16.  skip may alias out32
+// (the mid residual, col = 0, added in place).
+int op_unet_skip_join(const float* skip, long ld_skip, const void* res, int res_dt, int res_5d, int B, int F, int HW, int C2, float* out32,
+                      half_t* out16, long ld_out, int col, hipStream_t s);
+// conv_out: x fp16 NHWC [N][H][W][C] (normalised + activated), w fp32 [9][C][Cout] (op_pack_conv_w_direct), Cout <= 4 -> NCHW out_dt
+int op_unet_conv_out(const half_t* x, const float* w, const float* bias, void* out, int out_dt, int N, int H, int W, int C, int Cout,
+                     hipStream_t s);
+
+// ------------------------------------------------------------------------------------------
 // Conditioning-image preparation (model/ctrl_helper.py:268-296): Pillow-exact 8-bit Lanczos resize + /255 + NCHW + repeats
 //   src uint8 [F][Hin][Win][3]; h/v bounds int32 [out][2] + weights int32 [out][ks] (null = axis not resampled);
 //   tmp uint8 [F][Hin][W][3] (horizontal pass result); out [cfg][rep*F][3][H][W] in out_dtype
@@ -289,9 +307,9 @@ int op_prepare_images(const unsigned char* src, int F, int Hin, int Win, const i
 // and flush() launches what was deposited for one step -- as ONE grouped launch when the problems agree in shape and form,
 // one by one otherwise.  Every problem is computed exactly as it would be alone: results are bit-identical to the ungrouped forward.
 // ------------------------------------------------------------------------------------------
-struct GnStatsArgs { const void* x; int x_dtype; float* stats; int imgs, rows_per_img, C, G; };
+struct GnStatsArgs { const void* x; int x_dtype; float* stats; int imgs, rows_per_img, C, G; long ldx; };
 struct GnApplyArgs { const void* x; int x_dtype; const float* stats; const float* gamma; const float* beta; half_t* y;
-                     int imgs, rows_per_img, C, G; float eps; int silu; long ldy; int lo_off; long stat_rows, y_img_rows, y_row0; };
+                     int imgs, rows_per_img, C, G; float eps; int silu; long ldy; int lo_off; long stat_rows, y_img_rows, y_row0, ldx; };
 struct LnArgs { const void* x; int x_dtype; long ldx; const float* addv; long ldv; int rows_per_img, vmod; void* xsum;
                 const float* gamma; const float* beta; half_t* y; long ldy; int M, C; float eps; };
 int op_gn_stats_group(const GnStatsArgs* a, int n, hipStream_t s);

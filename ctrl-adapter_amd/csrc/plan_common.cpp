@@ -68,6 +68,21 @@ int build_temporal_tb(ParamSink& ps, const std::string& pre, int dim, int heads,
 
 // ------------------------------------------------------------------------------------------ runners
 int run_groupnorm(Ctx& cx, const Norm& n, const TV& x, half_t* y, int imgs, int rows, float eps, bool silu, bool split) {
+    if (n.C > 2048) {
+        // wider than the kernels' 256 lanes x 8 channels (the SVD UNet's 1280 + 1280 concatenation): the two column halves as two
+        // problems of 16 groups each over rows C elements apart -- a group never straddles the middle when C % 64 == 0
+        CTRL_CHECK(n.C % 64 == 0 && n.C <= 4096, "groupnorm: more than 2048 channels must be a multiple of 64, at most 4096");
+        const int Ch = n.C / 2;
+        const size_t esz = x.dt == DT_F32 ? 4 : 2;
+        for (int hf = 0; hf < 2; ++hf) {
+            const void* xh = (const char*)x.p + (size_t)hf * Ch * esz;
+            float* st = cx.stats(op_gn_stats_floats(imgs, rows, Ch, 16));
+            RUN(cx, op_gn_stats(xh, x.dt, st, imgs, rows, Ch, 16, cx.s, n.C));
+            RUN(cx, op_gn_apply(xh, x.dt, st, n.g + hf * Ch, n.b + hf * Ch, y + hf * Ch, imgs, rows, Ch, 16, eps, silu ? 1 : 0, cx.s,
+                                split ? 2 * n.C : n.C, split ? n.C : 0, 0, 0, 0, n.C));
+        }
+        return 0;
+    }
     if (op_gn_fused_applies(x.dt, rows, n.C, 32)) {      // small map: statistics + apply in one launch
         RUN(cx, op_gn_fused(x.p, x.dt, n.g, n.b, y, imgs, rows, n.C, 32, eps, silu ? 1 : 0, cx.s, split ? 2 * n.C : n.C, split ? n.C : 0));
         return 0;
@@ -117,10 +132,14 @@ int run_conv(Ctx& cx, const ConvW& c, const half_t* x, const TV& y, int N, int H
         g.mode = IG_CONV2D_PHASE; g.taps = 4; g.Ktot = 4 * c.Cin; g.W = c.w_phase;
     }
     g.bias = c.b; g.rowvec = o.rowvec; g.rowvec_ld = o.rowvec_ld; g.rows_per_img = Hout * Wout;
+    if (o.rowvec_rows > 0) {
+        CTRL_CHECK(!o.phase, "conv: the phase form takes one rowvec row per image");
+        g.rows_per_img = o.rowvec_rows;
+    }
     g.scale = 1.f; g.act = o.act; g.a_split = c.paired ? 2 : (c.dup ? 1 : 0);
     set_res(g, o.res, c.Cout);
     g.res_up = o.res_up;
-    set_out(g, y, c.Cout, c.Cout);
+    set_out(g, y, o.ldy ? o.ldy : c.Cout, c.Cout);
     return run_gemm(cx, g);
 }
 
@@ -141,14 +160,14 @@ int run_linear(Ctx& cx, const Lin& l, const half_t* x, long ldx, const TV& y, lo
 }
 
 int run_resnet(Ctx& cx, const ResnetW& w, const TV& x, const TV& out, int N, int H, int W, int up,
-               const float* temb_proj, int temb_ld, float eps) {
+               const float* temb_proj, int temb_ld, float eps, long ldy, int temb_rows) {
     const int Ho = H * up, Wo = W * up;
     const size_t m = cx.mark();
     half_t* a = cx.h((size_t)N * H * W * w.conv1.Cin);          // 2 x Cin wide for a split-operand conv1
     TRY(run_groupnorm(cx, w.norm1, x, a, N, H * W, eps, true, w.conv1.dup));
     // conv1 output feeds only GroupNorm: keep it in the stream dtype (its statistics are taken from this copy)
     TV h1 = cx.h1_f16 ? tv16(cx.h((size_t)N * Ho * Wo * w.Cout)) : stream_alloc(cx, (size_t)N * Ho * Wo * w.Cout, false);
-    ConvOpts o1; o1.up = up; o1.rowvec = temb_proj; o1.rowvec_ld = temb_ld;
+    ConvOpts o1; o1.up = up; o1.rowvec = temb_proj; o1.rowvec_ld = temb_ld; o1.rowvec_rows = temb_rows;
     // (the policy is read here, per forward: CTRL_CONV_UP_PHASE=0 is the A/B switch and the fallback to the 9-tap gather)
     o1.phase = up == 2 && w.conv1.w_phase != nullptr && !w.conv1.dup && !policy_is0(P_CONV_UP_PHASE);
     TRY(run_conv(cx, w.conv1, a, h1, N, H, W, o1));
@@ -169,7 +188,7 @@ int run_resnet(Ctx& cx, const ResnetW& w, const TV& x, const TV& out, int N, int
         sc = s2;
         sc_up = low ? 2 : 0;
     }
-    ConvOpts o2; o2.res = sc; o2.res_up = sc_up;
+    ConvOpts o2; o2.res = sc; o2.res_up = sc_up; o2.ldy = ldy;
     TRY(run_conv(cx, w.conv2, b, out, N, Ho, Wo, o2));
     cx.release(m);
     return 0;
@@ -365,8 +384,9 @@ int run_ffn(Ctx& cx, const Lin& ff1, const Lin& ff2, const half_t* xn, int dim, 
 }
 
 int run_basic_tb(Ctx& cx, const BasicTBW& w, const TV& X, const TV& out, int B, int L, const EhsCtx& e, const float* ov_pre,
-                 const PreKV* kv_pre, const half_t* X_ln) {
-    CTRL_CHECK(e.batch == 1 || e.batch == B, "encoder_hidden_states batch must be 1 or equal to the sample batch");
+                 const PreKV* kv_pre, const half_t* X_ln, int ov_rows) {
+    CTRL_CHECK(e.batch == 1 || e.batch == B || (ov_rows > 0 && ov_pre && e.Lk == 1),
+               "encoder_hidden_states batch must be 1 or equal to the sample batch");
     const size_t mk = cx.mark();
     const int M = B * L, dim = w.dim;
     const half_t* xn = X_ln;
@@ -384,7 +404,7 @@ int run_basic_tb(Ctx& cx, const BasicTBW& w, const TV& X, const TV& out, int B, 
         // attention's out-projection epilogue (per-image vector; one vector for all rows when the context is broadcast)
         float* ov = const_cast<float*>(ov_pre);
         if (!ov) TRY(single_key_vector(cx, w.attn2, dim, e, &ov));
-        TRY(run_self_attn(cx, w.attn1, xn, dim, X, x2, B, L, ov, e.batch == 1 ? M : L, &w.norm3, xn2));
+        TRY(run_self_attn(cx, w.attn1, xn, dim, X, x2, B, L, ov, ov_rows > 0 ? ov_rows : (e.batch == 1 ? M : L), &w.norm3, xn2));
         TRY(run_ff(cx, w.norm3, w.ff1, w.ff2, x2, dim, out, M, xn2));
     } else {
         TV x1 = stream_alloc(cx, (size_t)M * dim, false);

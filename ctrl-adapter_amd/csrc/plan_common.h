@@ -580,6 +580,8 @@ struct ConvOpts {
     int act = 0;
     int tap_origin = 0;        // 1: a 3x3 conv whose taps start at stride*o -- Downsample2D(padding=0) (ctrl_igemm_desc::tap_origin)
     bool phase = false;        // up == 2 on a 3x3 conv with a phase pack: four 2x2 convs over the source map (ctrl_igemm_desc::mode 3)
+    long ldy = 0;              // row stride of the output and its mirror (0 = the conv's Cout): the h half of a concatenated operand, in place
+    int rowvec_rows = 0;       // rows that share one rowvec row (0 = the output map, Hout * Wout; F * Hout * Wout: one vector per clip)
 };
 int run_conv(Ctx& cx, const ConvW& c, const half_t* x, const TV& y, int N, int Hin, int Win, const ConvOpts& o);
 // rowvec (optional): fp32 [M / rows_per_vec][rowvec_ld] added to every row of its group by the GEMM epilogue
@@ -592,8 +594,9 @@ int run_linear(Ctx& cx, const Lin& l, const half_t* x, long ldx, const TV& y, lo
                const float* blend_mix = nullptr, const TV& blend_other = TV(), const Norm* ln = nullptr, half_t* ln_out = nullptr);
 // out = ResnetBlock2D(x, temb); temb_proj = rowvec [N][ld] (already time_emb_proj(SiLU(emb)) incl. bias).
 // x.m16 must exist when the block has a shortcut conv (it is that conv's operand).
+// ldy: row stride of `out` (0 = Cout); temb_rows: rows per temb_proj row (0 = one per image)
 int run_resnet(Ctx& cx, const ResnetW& w, const TV& x, const TV& out, int N, int H, int W, int up,
-               const float* temb_proj, int temb_ld, float eps);
+               const float* temb_proj, int temb_ld, float eps, long ldy = 0, int temb_rows = 0);
 // Mid-block attention of the KL-VAE (diffusers Attention with its own GroupNorm, residual_connection, ONE head of dim C), shared by the
 // encoder and the decoder plans: out = to_out(softmax(Q K^T / sqrt(C)) V) + x over L tokens -- S = Q K^T on the GEMM in fp32, the row
 // softmax of vae.hip, O = P V against V^T, in query-row chunks whose S | P workspace stays under 256 MB
@@ -608,8 +611,9 @@ int project_text_kv(Ctx& cx, const AttnW& w, const EhsCtx& e, PreKV* out);
 // X [B*L][dim] stream -> out stream (out.m16 is filled when the caller needs a GEMM-operand copy)
 // ov_pre (optional, Lk == 1 only): the single-key cross-attention vector computed ahead of time (single_key_vector)
 // X_ln (optional): LayerNorm(norm1)(X) already computed by X's producer (run_linear(..., &w.norm1, X_ln))
+// ov_rows (Lk == 1 with ov_pre): rows that share one row of ov_pre (0 = all rows for a broadcast context, else one image's L)
 int run_basic_tb(Ctx& cx, const BasicTBW& w, const TV& X, const TV& out, int B, int L, const EhsCtx& e, const float* ov_pre = nullptr,
-                 const PreKV* kv_pre = nullptr, const half_t* X_ln = nullptr);
+                 const PreKV* kv_pre = nullptr, const half_t* X_ln = nullptr, int ov_rows = 0);
 // [e.batch][dim] fp32 output of a one-key cross-attention (query independent, note N5)
 int single_key_vector(Ctx& cx, const AttnW& w, int dim, const EhsCtx& e, float** out);
 int run_layernorm(Ctx& cx, const Norm& n, const TV& x, half_t* y, int M, int dim);

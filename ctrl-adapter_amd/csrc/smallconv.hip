@@ -11,10 +11,11 @@
 
 namespace {
 
-template <int CIN, int COT, bool NCHW_IN>
+// F32_OUT: the output rows in fp32 (the UNet's stem writes its residual stream), else fp16
+template <int CIN, int COT, bool NCHW_IN, bool F32_OUT = false>
 __global__ __launch_bounds__(256) void conv3x3_direct_kernel(const void* __restrict__ in, int in_dt,
                                                              const float* __restrict__ w, const float* __restrict__ bias,
-                                                             half_t* __restrict__ out, int N, int Cout, int Hin, int Win,
+                                                             void* __restrict__ out, int N, int Cout, int Hin, int Win,
                                                              int Hout, int Wout, int stride, int silu) {
     const size_t npix = (size_t)N * Hout * Wout;
     const size_t pix = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -53,7 +54,18 @@ __global__ __launch_bounds__(256) void conv3x3_direct_kernel(const void* __restr
 #pragma unroll
             for (int c = 0; c < COT; ++c) acc[c] += xin[ci] * wt[(size_t)ci * Cout + c];
     }
-    half_t* op = out + pix * Cout + co0;
+    if (F32_OUT) {
+        float* fp = (float*)out + pix * Cout + co0;
+#pragma unroll
+        for (int c4 = 0; c4 < COT / 4; ++c4) {
+            f4 o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = silu ? silu_f(acc[c4 * 4 + j]) : acc[c4 * 4 + j];
+            *(f4*)(fp + c4 * 4) = o;
+        }
+        return;
+    }
+    half_t* op = (half_t*)out + pix * Cout + co0;
 #pragma unroll
     for (int c8 = 0; c8 < COT / 8; ++c8) {
         h8 o;
@@ -171,7 +183,7 @@ int launch_direct(const void* in, int in_dt, const float* w, const float* bias, 
     PROF_WORK(0, 2.0 * ((double)N * Hin * Win * CIN + (double)npix * Cout));
     prof_detail("N%d %d->%d %dx%d s%d%s", N, CIN, Cout, Hin, Win, stride, NCHW_IN ? " nchw" : "");
     LAUNCH("conv3x3_direct", (conv3x3_direct_kernel<CIN, COT, NCHW_IN>), grid, dim3(256), 0, s,
-           in, in_dt, w, bias, out, N, Cout, Hin, Win, Hout, Wout, stride, silu);
+           in, in_dt, w, bias, (void*)out, N, Cout, Hin, Win, Hout, Wout, stride, silu);
     return 0;
 }
 
@@ -196,6 +208,23 @@ int op_conv3x3_direct(const void* in, int in_dtype, int in_nchw, const float* w,
               "); supported: NCHW Cin 3|4, NHWC Cin 16|32");
 }
 
+
+// the UNet stem: NCHW sample [N][8][H][W] (any dtype) -> fp32 NHWC rows [N*H*W][Cout]; w fp32 [9][8][Cout], stride 1, no activation
+int op_conv3x3_direct_f32(const void* in, int in_dtype, const float* w, const float* bias, float* out, int N, int Cin, int Cout, int H,
+                          int W, hipStream_t s) {
+    CTRL_CHECK(Cin == 8, "conv3x3_direct_f32: Cin must be 8 (the SVD UNet's stem)");
+    CTRL_CHECK(Cout % 16 == 0 && ((uintptr_t)out & 15) == 0, "conv3x3_direct_f32: Cout must be a multiple of 16, out 16-byte aligned");
+    const size_t npix = (size_t)N * H * W;
+    PROF_WORK(0, (double)npix * ((in_dtype == DT_F32 ? 4.0 : 2.0) * Cin + 4.0 * Cout));
+    prof_detail("N%d %d->%d %dx%d nchw f32", N, Cin, Cout, H, W);
+    if (Cout % 32 == 0)
+        LAUNCH("conv3x3_direct", (conv3x3_direct_kernel<8, 32, true, true>), dim3((unsigned)((npix + 255) / 256), Cout / 32), dim3(256), 0, s,
+               in, in_dtype, w, bias, (void*)out, N, Cout, H, W, H, W, 1, 0);
+    else
+        LAUNCH("conv3x3_direct", (conv3x3_direct_kernel<8, 16, true, true>), dim3((unsigned)((npix + 255) / 256), Cout / 16), dim3(256), 0, s,
+               in, in_dtype, w, bias, (void*)out, N, Cout, H, W, H, W, 1, 0);
+    return 0;
+}
 
 bool op_conv3x3_small_mfma_applies(int Cin, int Cout) { return (Cin == 16 || Cin == 32) && (Cout == 16 || Cout == 32); }
 

@@ -719,6 +719,49 @@ int ctrl_vae_tdecoder_forward(ctrl_vae_tdecoder* h, const void* latents, int lat
 int ctrl_op_vae_time_conv(const float* x, const float* w, const float* b, int F, int H, int W, int Cout, int kind, void* out,
                           int out_dtype, void* stream);
 
+/* ---- SVD backbone UNet (diffusers UNetSpatioTemporalConditionModel with the reference's two ControlNet-residual kwargs) ---- */
+typedef struct ctrl_unet_st_config {
+    int32_t in_channels;                           /* 8 */
+    int32_t out_channels;                          /* 1..4 */
+    int32_t num_levels;                            /* len(block_out_channels), 1..4 */
+    int32_t block_out_channels[4];                 /* multiples of 64 */
+    int32_t layers_per_block;                      /* down blocks hold this many ResNets, up blocks one more */
+    int32_t transformer_layers_per_block;
+    int32_t num_attention_heads[4];                /* per level; out_channels / heads must be 64 where the level (or the mid block) attends */
+    int32_t cross_attention_dim;
+    int32_t level_has_attn[4];                     /* down block i is CrossAttnDownBlockSpatioTemporal (up block levels-1-i mirrors it) */
+    int32_t addition_time_embed_dim;
+    int32_t projection_class_embeddings_input_dim;
+} ctrl_unet_st_config;
+typedef struct ctrl_unet_st ctrl_unet_st;   /* opaque */
+/* parameters: diffusers' keys (conv_in.*, time_embedding.linear_{1,2}.*, add_embedding.linear_{1,2}.*,
+   {down,up}_blocks.{i}.resnets.{j}.{spatial_res_block,temporal_res_block}.*, ....resnets.{j}.time_mixer.mix_factor,
+   ....attentions.{j}.{norm,proj_in,proj_out}.*, ....attentions.{j}.time_pos_embed.linear_{1,2}.*, ....attentions.{j}.time_mixer.mix_factor,
+   ....attentions.{j}.transformer_blocks.{k}.*, ....attentions.{j}.temporal_transformer_blocks.{k}.*, ....downsamplers.0.conv.*,
+   ....upsamplers.0.conv.*, mid_block.*, conv_norm_out.*, conv_out.*) */
+int ctrl_unet_st_param_count(const ctrl_unet_st_config* cfg);
+int ctrl_unet_st_param_spec(const ctrl_unet_st_config* cfg, int i, char* name, int name_len, int64_t shape[6], int* ndim);
+int ctrl_unet_st_create(const ctrl_unet_st_config* cfg, const ctrl_tensor_ref* tensors, int n_tensors, void* stream, ctrl_unet_st** out);
+void ctrl_unet_st_destroy(ctrl_unet_st* h);
+/* what plan creation selected, as one text line */
+int ctrl_unet_st_selection(ctrl_unet_st* h, char* buf, int len);
+/* sample [B][F][in_channels][h][w] (CTRL_F32 / F16 / BF16) -> out [B][F][out_channels][h][w] in the same dtype.  timesteps: fp32 device,
+   1 or B values; encoder_hidden_states [B][1][cross_attention_dim] (one key); added_time_ids fp32 device [B][n_time_ids].
+   down_residuals (host array of n_down_residuals device pointers, may be 0): residual i is added to skip i -- skip 0 is conv_in's output,
+   then every down block's ResNet / transformer outputs and its down-sampler's -- all in one dtype and one layout: (b f) c h w
+   (down_5d = 0) or b c f h w (down_5d = 1).  mid_residual (may be NULL) likewise, added to the mid block's output.  h and w must be
+   multiples of 2^(num_levels - 1), F <= 32.  The first forward of a larger size allocates the workspace (not under stream capture);
+   every later one is capturable: one stream, no side lanes. */
+int ctrl_unet_st_forward(ctrl_unet_st* h, const void* sample, int sample_dtype, int B, int F, int lat_h, int lat_w, const float* timesteps,
+                         int t_count, const void* encoder_hidden_states, int ehs_dtype, const float* added_time_ids, int n_time_ids,
+                         const void* const* down_residuals, int n_down_residuals, int down_dtype, int down_5d, const void* mid_residual,
+                         int mid_dtype, int mid_5d, void* out, void* stream);
+/* op level (csrc/unet.hip): one skip tensor of the up path.  out32[r][col + c] = skip[r][c] (+ res(b, f, c, p)) for the B * F * HW rows
+   r = (b F + f) HW + p and c < C2 (a multiple of 32), and out16 (may be NULL) its fp16 rounding; skip rows ld_skip floats apart, out rows
+   ld_out elements.  res (may be NULL): (b f) c h w (res_5d = 0) or b c f h w (res_5d = 1) in res_dtype.  skip may be out32 with col = 0. */
+int ctrl_op_unet_skip_join(const float* skip, int64_t ld_skip, const void* res, int res_dtype, int res_5d, int B, int F, int HW, int C2,
+                           float* out32, void* out16, int64_t ld_out, int col, void* stream);
+
 /* ---- Router (model/ctrl_router.py) ---- */
 /* weights_out fp32 device [num_routers + (has_mid?1:0)][E]; wg fp32 device same shape (Linear(1,E).weight[:,0]
  * per router; ignored for equal_weights); mask host int[E] (NULL = all ones). */

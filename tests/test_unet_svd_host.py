@@ -1,0 +1,242 @@
+"""SVD's backbone UNet, host side (no GPU): the parameter inventory against the restatement's diffusers keys (tests/unet_svd_ref.py) for
+the three test configs, the C struct's size, the new symbols, persistence, the forward signature, every refusal, and the restatement
+held against oracle/blocks.py: with every mix factor at +40 (sigmoid = 1 in fp32: the temporal branches are switched off) a restated
+SpatioTemporalResBlock is the oracle's ResnetBlock2D and a restated TransformerSpatioTemporalModel is GroupNorm -> Linear ->
+BasicTransformerBlock -> Linear + input, bit for bit; all-zero residuals equal no residuals; the 5-D and 4-D layouts agree."""
+import ctypes
+import inspect
+import os
+import subprocess
+import sys
+
+import pytest
+import torch
+
+import unet_svd_ref as R
+from helpers import ROOT
+from oracle.blocks import ResnetBlock2D
+
+CFGS = sorted(R.CONFIGS)
+# two levels of NARROW's widths: what the persistence and the restatement-only tests need, at a tenth of the parameters
+TINY = dict(R.NARROW, block_out_channels=(64, 128), num_attention_heads=(1, 2),
+            down_block_types=("CrossAttnDownBlockSpatioTemporal", "DownBlockSpatioTemporal"),
+            up_block_types=("UpBlockSpatioTemporal", "CrossAttnUpBlockSpatioTemporal"))
+
+
+def _shapes(sd):
+    return {k: tuple(v.shape) for k, v in sd.items()}
+
+
+@pytest.mark.parametrize("name", CFGS)
+def test_param_spec_equals_diffusers_keys(name):
+    import ctrl_adapter_amd as P
+    from ctrl_adapter_amd.unet_spatio_temporal import unet_st_spec
+    cfg = R.CONFIGS[name]
+    with torch.device("meta"):
+        ref = R.UNetSvdRef(**cfg)
+    m = P.UNetSpatioTemporalConditionModel(**cfg)
+    want = _shapes(ref.state_dict())
+    spec = unet_st_spec(m._cfg)
+    assert len(spec) == len(dict(spec)) and dict(spec) == want
+    sd = _shapes(m.state_dict())
+    assert sd == want
+    boc = cfg["block_out_channels"]
+    # first up ResNet: the mid block's channels + the last skip's; last up ResNet: the level-0 stream + conv_in's output
+    assert sd["up_blocks.0.resnets.0.spatial_res_block.conv1.weight"] == (boc[-1], boc[-1] + boc[-1], 3, 3)
+    last = "up_blocks.%d.resnets.%d" % (len(boc) - 1, cfg["layers_per_block"])
+    assert sd[last + ".spatial_res_block.conv1.weight"] == (boc[0], boc[0] + boc[0], 3, 3)
+    if len(boc) > 1:         # the first ResNet of the last up block: Cprev (level 1) + Cskip (level 0)
+        assert sd["up_blocks.%d.resnets.0.spatial_res_block.conv1.weight" % (len(boc) - 1)] == (boc[0], boc[1] + boc[0], 3, 3)
+        assert sd["up_blocks.%d.resnets.0.spatial_res_block.conv_shortcut.weight" % (len(boc) - 1)] == (boc[0], boc[1] + boc[0], 1, 1)
+    assert sd["down_blocks.0.resnets.0.temporal_res_block.conv1.weight"] == (boc[0], boc[0], 3, 1, 1)
+    assert sd["mid_block.resnets.1.time_mixer.mix_factor"] == (1,) and sd["down_blocks.0.attentions.0.time_mixer.mix_factor"] == (1,)
+    assert sd["conv_in.weight"] == (boc[0], 8, 3, 3) and sd["conv_out.weight"] == (4, boc[0], 3, 3)
+    assert sd["add_embedding.linear_1.weight"] == (4 * boc[0], cfg["projection_class_embeddings_input_dim"])
+    assert sd["down_blocks.0.attentions.0.time_pos_embed.linear_2.weight"] == (boc[0], 4 * boc[0])
+    assert sd["mid_block.attentions.0.temporal_transformer_blocks.0.ff_in.net.0.proj.weight"] == (8 * boc[-1], boc[-1])
+
+
+def test_config_struct_size_matches_the_header_and_symbols_resolve(tmp_path):
+    from ctrl_adapter_amd import _lib
+    src = tmp_path / "size.c"
+    src.write_text('#include <stdio.h>\n#include "ctrl_hip.h"\nint main(void) { printf("%zu\\n", sizeof(ctrl_unet_st_config)); return 0; }\n')
+    exe = tmp_path / "size"
+    cc = next((c for c in ("cc", "gcc", "clang", "/opt/rocm/llvm/bin/clang") if subprocess.call(["sh", "-c", "command -v %s >/dev/null" % c]) == 0), None)
+    assert cc is not None, "no C compiler"
+    subprocess.check_call([cc, "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    assert int(subprocess.check_output([str(exe)]).decode()) == ctypes.sizeof(_lib.UNetSTConfig)
+    lib = _lib.lib()
+    for name in ("ctrl_unet_st_param_count", "ctrl_unet_st_param_spec", "ctrl_unet_st_create", "ctrl_unet_st_destroy", "ctrl_unet_st_selection",
+                 "ctrl_unet_st_forward", "ctrl_op_unet_skip_join"):
+        assert hasattr(lib, name) and name in _lib.EXPORTS
+    assert _lib.ABI_VERSION == 7 and lib.ctrl_abi_version() == 7
+
+
+def test_state_dict_and_save_pretrained_round_trip(tmp_path):
+    import ctrl_adapter_amd as P
+    ref = R.seeded_unet(TINY, 11)
+    mixes = {float(v) for k, v in ref.state_dict().items() if k.endswith("mix_factor")}
+    assert mixes == set(R.MIX_CYCLE)                         # seeded_unet does not leave every mix factor at its init value
+    m = P.UNetSpatioTemporalConditionModel(**TINY, sample_size=96, num_frames=14)
+    m.load_state_dict(ref.state_dict())
+    for k, v in ref.state_dict().items():
+        assert torch.equal(m.state_dict()[k], v), k
+    m.save_pretrained(str(tmp_path))
+    m2 = P.UNetSpatioTemporalConditionModel.from_pretrained(str(tmp_path), torch_dtype=torch.float16)
+    assert m2.dtype == torch.float16 and m2.device.type == "cpu"
+    assert m2.config.sample_size == 96 and m2.config.num_frames == 14 and tuple(m2.config.block_out_channels) == TINY["block_out_channels"]
+    assert set(m2.state_dict()) == set(ref.state_dict())
+    for k, v in ref.state_dict().items():
+        assert torch.equal(m2.state_dict()[k].float(), v), k
+
+
+def test_forward_signature_is_the_references():
+    import ctrl_adapter_amd as P
+    names = list(inspect.signature(P.UNetSpatioTemporalConditionModel.forward).parameters)
+    assert names == ["self", "sample", "timestep", "encoder_hidden_states", "added_time_ids", "down_block_additional_residuals",
+                     "mid_block_additional_residual", "return_dict"]
+    assert list(inspect.signature(R.UNetSvdRef.forward).parameters)[:len(names)] == names
+    ctor = list(inspect.signature(P.UNetSpatioTemporalConditionModel.__init__).parameters)
+    assert ctor == ["self", "sample_size", "in_channels", "out_channels", "down_block_types", "up_block_types", "block_out_channels",
+                    "addition_time_embed_dim", "projection_class_embeddings_input_dim", "layers_per_block", "cross_attention_dim",
+                    "transformer_layers_per_block", "num_attention_heads", "num_frames"]
+    out = P.UNetSpatioTemporalConditionOutput(torch.zeros(1))
+    assert isinstance(out, tuple) and out[0] is out.sample and len(out) == 1
+    m = P.UNetSpatioTemporalConditionModel(**R.NARROW)
+    assert m.dtype == torch.float32 and m.device.type == "cpu" and m.config.in_channels == 8
+
+
+_REFUSED = r"^UNetSpatioTemporalConditionModel \(libctrlhip\): "
+
+
+def test_constructor_refusals():
+    import ctrl_adapter_amd as P
+    U = P.UNetSpatioTemporalConditionModel
+    with pytest.raises(ValueError, match=_REFUSED + ".*attention_head_dim"):
+        U(**dict(R.NARROW, num_attention_heads=(2, 2, 4, 4)))                # 64 // 2 = 32 at level 0
+    with pytest.raises(ValueError, match=_REFUSED + ".*attention_head_dim"):
+        U(**dict(R.NARROW, num_attention_heads=(1, 2, 4, 8)))                # the last level has no attention, the mid block uses its heads
+    with pytest.raises(ValueError, match=_REFUSED + ".*num_frames"):
+        U(**R.NARROW, num_frames=33)
+    with pytest.raises(ValueError, match=_REFUSED + ".*block type"):
+        U(**dict(R.NARROW, down_block_types=("CrossAttnDownBlock2D",) * 3 + ("DownBlockSpatioTemporal",)))
+    with pytest.raises(ValueError, match=_REFUSED + ".*block type"):
+        U(**dict(R.NARROW, up_block_types=("UpBlock3D",) + ("CrossAttnUpBlockSpatioTemporal",) * 3))
+    with pytest.raises(ValueError, match=_REFUSED + ".*mirror"):
+        U(**dict(R.NARROW, up_block_types=("CrossAttnUpBlockSpatioTemporal",) * 3 + ("UpBlockSpatioTemporal",)))
+    U(**R.NARROW, num_frames=32)
+
+
+class _OnGpu:
+    """a module that says it lives on the GPU: forward's input checks run (and refuse) before anything touches a device"""
+
+    def __init__(self, m):
+        self.m = m
+
+    def __enter__(self):
+        type(self.m).device = property(lambda s: torch.device("cuda", 0))
+        return self.m
+
+    def __exit__(self, *a):
+        del type(self.m).device
+
+
+def test_forward_refusals_run_before_any_launch():
+    import ctrl_adapter_amd as P
+
+    class U(P.UNetSpatioTemporalConditionModel):       # (a subclass, so the patched `device` does not leak into the package's class)
+        pass
+
+    class FakeCuda(torch.Tensor):
+        """a CPU tensor that reports itself on cuda:0"""
+        is_cuda = property(lambda s: True)
+        device = property(lambda s: torch.device("cuda", 0))
+
+    def fake(*shape):
+        return torch.zeros(*shape).as_subclass(FakeCuda)
+
+    with _OnGpu(U(**R.NARROW)) as m:
+        ehs, ids = fake(2, 1, 64), fake(2, 3)
+        with pytest.raises(ValueError, match=_REFUSED + ".*multiples of 8"):
+            m(fake(2, 3, 8, 12, 16), 5.0, ehs, ids)
+        with pytest.raises(ValueError, match=_REFUSED + ".*multiples of 8"):
+            m(fake(2, 3, 8, 16, 20), 5.0, ehs, ids)
+        with pytest.raises(ValueError, match=_REFUSED + ".*at most 32 frames"):
+            m(fake(2, 33, 8, 16, 16), 5.0, ehs, ids)
+        with pytest.raises(ValueError, match=_REFUSED + ".*keys"):
+            m(fake(2, 3, 8, 16, 16), 5.0, fake(2, 77, 64), ids)
+        with pytest.raises(ValueError, match=_REFUSED + ".*sample must be"):
+            m(fake(2, 3, 4, 16, 16), 5.0, ehs, ids)
+        with pytest.raises(ValueError, match=_REFUSED + ".*added_time_ids"):
+            m(fake(2, 3, 8, 16, 16), 5.0, ehs, fake(2, 2))
+    m = P.UNetSpatioTemporalConditionModel(**R.NARROW)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        m(torch.zeros(2, 3, 8, 16, 16), 5.0, torch.zeros(2, 1, 64), torch.zeros(2, 3))
+
+
+# ------------------------------------------------------------------------------------------------ the restatement against the oracle's blocks
+def test_restated_st_res_block_with_the_temporal_branch_off_is_the_oracles_resnet():
+    from ctrl_adapter_amd.synthetic import seeded_init
+    blk = seeded_init(R.SpatioTemporalResBlock(96, 64, 128, 1e-6), seed=5).eval()
+    with torch.no_grad():
+        blk.time_mixer.mix_factor.fill_(40.0)                 # sigmoid(40) == 1.0 in fp32: alpha * spatial + 0 * temporal
+    plain = ResnetBlock2D(in_channels=96, out_channels=64, temb_channels=128, eps=1e-6).eval()
+    plain.load_state_dict(blk.spatial_res_block.state_dict())
+    g = torch.Generator().manual_seed(1)
+    x, temb = torch.randn(6, 96, 5, 7, generator=g), torch.randn(6, 128, generator=g)
+    with torch.no_grad():
+        assert float(torch.sigmoid(blk.time_mixer.mix_factor)) == 1.0
+        got = blk(x, temb, torch.zeros(2, 3))
+        assert torch.equal(got, plain(x, temb))
+        blk.time_mixer.mix_factor.fill_(0.5)
+        assert not torch.equal(blk(x, temb, torch.zeros(2, 3)), got)      # the temporal branch is there
+
+
+def test_restated_transformer_with_the_temporal_branch_off_is_norm_linear_block_linear():
+    from ctrl_adapter_amd.synthetic import seeded_init
+    t = seeded_init(R.TransformerSpatioTemporalModel(2, 64, 128, 1, 64), seed=6).eval()
+    with torch.no_grad():
+        t.time_mixer.mix_factor.fill_(40.0)
+    g = torch.Generator().manual_seed(2)
+    x, ehs = torch.randn(6, 128, 3, 4, generator=g), torch.randn(2, 1, 64, generator=g).repeat_interleave(3, dim=0)
+    with torch.no_grad():
+        got = t(x, ehs, torch.zeros(2, 3))
+        h = t.norm(x).permute(0, 2, 3, 1).reshape(6, 12, 128)
+        h = t.proj_out(t.transformer_blocks[0](t.proj_in(h), encoder_hidden_states=ehs))
+        want = h.reshape(6, 3, 4, 128).permute(0, 3, 1, 2) + x
+        assert torch.equal(got, want)
+        t.time_mixer.mix_factor.fill_(0.5)
+        assert not torch.equal(t(x, ehs, torch.zeros(2, 3)), got)
+
+
+_REF = {}
+
+
+def _tiny():
+    if not _REF:
+        _REF["m"] = R.seeded_unet(TINY, 21)
+    return _REF["m"]
+
+
+def test_restated_forward_zero_residuals_equal_none_and_layouts_agree():
+    ref = _tiny()
+    B, F, h, w = 1, 2, 8, 8
+    inp = R.seeded_inputs(TINY, B, F, h, w, seed=4, residuals="4d", res_dtype=torch.float32)
+    inp5 = R.seeded_inputs(TINY, B, F, h, w, seed=4, residuals="5d", res_dtype=torch.float32)
+    assert inp5["down_block_additional_residuals"][0].shape == (B, 64, F, h, w)
+    plain = {k: v for k, v in inp.items() if "residual" not in k}
+    with torch.no_grad():
+        base, stages = ref(**plain, return_stages=True)
+        zeros = dict(plain, down_block_additional_residuals=[torch.zeros_like(r) for r in inp["down_block_additional_residuals"]],
+                     mid_block_additional_residual=torch.zeros_like(inp["mid_block_additional_residual"]))
+        assert torch.equal(ref(**zeros).sample, base)
+        with4 = ref(**inp).sample
+        assert torch.equal(ref(**inp5).sample, with4)
+        assert not torch.equal(with4, base)
+        assert base.shape == (B, F, 4, h, w)
+    shapes, mid = R.skip_shapes(TINY, B, F, h, w)
+    assert [tuple(s.shape[1:]) for s in stages["skips"]] == shapes and tuple(stages["mid"].shape[1:]) == mid
+    assert len(stages["ups"]) == 2 and stages["ups"][-1].shape == (B * F, 64, h, w)
+    # a timestep as a Python number gives what the [B] tensor of the same value gives
+    with torch.no_grad():
+        assert torch.equal(ref(**dict(plain, timestep=37.0), return_dict=False)[0], base)
