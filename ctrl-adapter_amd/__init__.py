@@ -13,3 +13,4 @@ from .vae_encoder import AutoencoderKLEncoder, encode_svd_image_latents, prepare
 from .vae_decoder import AutoencoderKL, AutoencoderKLDecoder, DecoderOutput, decode_i2vgen_latents, decode_sdxl_latents  # noqa: F401
 from .vae_temporal_decoder import AutoencoderKLTemporalDecoder, decode_svd_latents  # noqa: F401
 from .unet_spatio_temporal import UNetSpatioTemporalConditionModel, UNetSpatioTemporalConditionOutput  # noqa: F401
+from .unet_2d_condition import UNet2DConditionModel, UNet2DConditionOutput  # noqa: F401

@@ -250,7 +250,7 @@ int op_router_softmax(const float* wg, const int* mask, float* out, int R, int E
 int op_conv3x3_direct(const void* in, int in_dtype, int in_nchw, const float* w, const float* bias, half_t* out,
                       int N, int Cin, int Cout, int Hin, int Win, int stride, int silu, hipStream_t s);
 
-// the SVD UNet's stem (Cin = 8): NCHW sample of any dtype -> fp32 NHWC rows (the residual stream), stride 1, no activation
+// the UNets' stems (Cin = 8: SVD, Cin = 4: SDXL): NCHW sample of any dtype -> fp32 NHWC rows (the residual stream), stride 1, no activation
 int op_conv3x3_direct_f32(const void* in, int in_dtype, const float* w, const float* bias, float* out, int N, int Cin, int Cout, int H,
                           int W, hipStream_t s);
 
@@ -278,17 +278,23 @@ int op_pack_linear_w(const void* w, int dtype, half_t* out, int N, int K, int ge
 int op_pack_vec(const void* v, int dtype, float* out, int N, int geglu, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
-// SVD backbone UNet (unet.hip)
+// Backbone UNets: SVD and SDXL (unet.hip)
 // ------------------------------------------------------------------------------------------
 // one skip tensor of the up path: out[r][col + c] = skip[r][c] (+ res(b, f, c, p)) for the B * F * HW rows r = (b F + f) HW + p and
 // c < C2, the fp32 master (row stride ld_out) and, when out16 is given, its fp16 mirror with one rounding.  res (optional): the adapter's
 // residual as the caller holds it, (b f) c h w (res_5d = 0) or b c f h w (res_5d = 1), fp32 / fp16 / bf16.  skip may alias out32
 // (the mid residual, col = 0, added in place).
+// lo_off > 0: the mirror is a split [hi | lo] row pair -- rows 2 * ld_out halves apart, lo = fp16(x - hi) at column lo_off + col + c
 int op_unet_skip_join(const float* skip, long ld_skip, const void* res, int res_dt, int res_5d, int B, int F, int HW, int C2, float* out32,
-                      half_t* out16, long ld_out, int col, hipStream_t s);
+                      half_t* out16, long ld_out, int col, hipStream_t s, int lo_off = 0);
 // conv_out: x fp16 NHWC [N][H][W][C] (normalised + activated), w fp32 [9][C][Cout] (op_pack_conv_w_direct), Cout <= 4 -> NCHW out_dt
 int op_unet_conv_out(const half_t* x, const float* w, const float* bias, void* out, int out_dt, int N, int H, int W, int C, int Cout,
                      hipStream_t s);
+
+// the operand rows of add_embedding.linear_1 of a text_time UNet (SDXL): out fp32 [B][ld_out], columns [0, text_dim) = text_embeds[b]
+// (fp32 / fp16 / bf16) converted, columns text_dim + i * dim + [0, dim) = [cos | sin] of time_ids[b][i] (sincos_kernel's arithmetic)
+int op_unet_text_time(const void* text, int text_dt, int text_dim, const float* ids, int n_ids, int dim, float* out, long ld_out, int B,
+                      hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
 // Conditioning-image preparation (model/ctrl_helper.py:268-296): Pillow-exact 8-bit Lanczos resize + /255 + NCHW + repeats

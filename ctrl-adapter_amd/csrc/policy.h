@@ -33,7 +33,7 @@ enum PolicyKey {
     P_MULTI_CN_LANES,          // CTRL_MULTI_CN_LANES=0: MultiControlNetModel runs its nets one after the other (read by the Python mirror)
     P_CN_BATCH_LANES,          // CTRL_CN_BATCH_LANES=1: ControlNetModel.forward splits a batch >= 8 over two stream lanes (Python mirror; measured: no gain)
     P_CONV_UP_PHASE,           // CTRL_CONV_UP_PHASE=0: conv1 of an up-sampling ResNet keeps the 9-tap gather over the x2 map (default: four 2x2 phase convs)
-    P_UNET_SPLIT,              // CTRL_UNET_SPLIT=1: split [hi | lo] operands for the SVD UNet's ResNet convolutions (default: plain fp16 operands)
+    P_UNET_SPLIT,              // CTRL_UNET_SPLIT=1: split [hi | lo] operands for the backbone UNets' (SVD, SDXL) ResNet convolutions (default: plain fp16 operands)
     P_COUNT
 };
 // the variable's value as getenv() would return it (nullptr = unset), from the table: environment snapshot or ctrl_policy_set override

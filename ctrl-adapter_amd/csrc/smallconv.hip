@@ -209,21 +209,28 @@ int op_conv3x3_direct(const void* in, int in_dtype, int in_nchw, const float* w,
 }
 
 
-// the UNet stem: NCHW sample [N][8][H][W] (any dtype) -> fp32 NHWC rows [N*H*W][Cout]; w fp32 [9][8][Cout], stride 1, no activation
-int op_conv3x3_direct_f32(const void* in, int in_dtype, const float* w, const float* bias, float* out, int N, int Cin, int Cout, int H,
-                          int W, hipStream_t s) {
-    CTRL_CHECK(Cin == 8, "conv3x3_direct_f32: Cin must be 8 (the SVD UNet's stem)");
-    CTRL_CHECK(Cout % 16 == 0 && ((uintptr_t)out & 15) == 0, "conv3x3_direct_f32: Cout must be a multiple of 16, out 16-byte aligned");
+// the UNet stems: NCHW sample [N][Cin][H][W] (any dtype; Cin = 8: SVD, 4: SDXL) -> fp32 NHWC rows [N*H*W][Cout]; w fp32 [9][Cin][Cout],
+// stride 1, no activation
+template <int CIN>
+static int launch_stem_f32(const void* in, int in_dtype, const float* w, const float* bias, float* out, int N, int Cout, int H, int W, hipStream_t s) {
     const size_t npix = (size_t)N * H * W;
-    PROF_WORK(0, (double)npix * ((in_dtype == DT_F32 ? 4.0 : 2.0) * Cin + 4.0 * Cout));
-    prof_detail("N%d %d->%d %dx%d nchw f32", N, Cin, Cout, H, W);
+    PROF_WORK(0, (double)npix * ((in_dtype == DT_F32 ? 4.0 : 2.0) * CIN + 4.0 * Cout));
+    prof_detail("N%d %d->%d %dx%d nchw f32", N, CIN, Cout, H, W);
     if (Cout % 32 == 0)
-        LAUNCH("conv3x3_direct", (conv3x3_direct_kernel<8, 32, true, true>), dim3((unsigned)((npix + 255) / 256), Cout / 32), dim3(256), 0, s,
+        LAUNCH("conv3x3_direct", (conv3x3_direct_kernel<CIN, 32, true, true>), dim3((unsigned)((npix + 255) / 256), Cout / 32), dim3(256), 0, s,
                in, in_dtype, w, bias, (void*)out, N, Cout, H, W, H, W, 1, 0);
     else
-        LAUNCH("conv3x3_direct", (conv3x3_direct_kernel<8, 16, true, true>), dim3((unsigned)((npix + 255) / 256), Cout / 16), dim3(256), 0, s,
+        LAUNCH("conv3x3_direct", (conv3x3_direct_kernel<CIN, 16, true, true>), dim3((unsigned)((npix + 255) / 256), Cout / 16), dim3(256), 0, s,
                in, in_dtype, w, bias, (void*)out, N, Cout, H, W, H, W, 1, 0);
     return 0;
+}
+
+int op_conv3x3_direct_f32(const void* in, int in_dtype, const float* w, const float* bias, float* out, int N, int Cin, int Cout, int H,
+                          int W, hipStream_t s) {
+    CTRL_CHECK(Cin == 8 || Cin == 4, "conv3x3_direct_f32: Cin must be 8 (the SVD UNet's stem) or 4 (the SDXL UNet's)");
+    CTRL_CHECK(Cout % 16 == 0 && ((uintptr_t)out & 15) == 0, "conv3x3_direct_f32: Cout must be a multiple of 16, out 16-byte aligned");
+    return Cin == 8 ? launch_stem_f32<8>(in, in_dtype, w, bias, out, N, Cout, H, W, s)
+                    : launch_stem_f32<4>(in, in_dtype, w, bias, out, N, Cout, H, W, s);
 }
 
 bool op_conv3x3_small_mfma_applies(int Cin, int Cout) { return (Cin == 16 || Cin == 32) && (Cout == 16 || Cout == 32); }

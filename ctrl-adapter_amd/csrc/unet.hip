@@ -1,8 +1,10 @@
-// Kernels of the SVD backbone UNet (plan_unet_st.cpp; gfx950) that no other plan has:
+// Kernels of the backbone UNets (SVD: plan_unet_st.cpp, SDXL: plan_unet2d.cpp; gfx950) that no other plan has:
 //   unet_skip_join_kernel   one skip tensor of the up path: fp32 NHWC skip (+ the adapter's residual, read in the caller's NCHW / NCFHW
 //                           layout) -> columns [col, col + C2) of the up ResNet's concatenated operand, fp32 master + fp16 mirror
 //   unet_conv_out_kernel    conv_out 3x3, C0 -> <= 4 channels, on the normalised + activated fp16 map -> NCHW in the sample's dtype
-// Both are HBM-bound: the join moves 4 (skip) + 2..4 (residual) + 6 (master + mirror) bytes per element once; conv_out reads the C0-wide
+//   unet_text_time_kernel   SDXL's text_time addition embedding: the operand rows of add_embedding.linear_1, [text_embeds | sinusoids of
+//                           the time ids], in one launch (a few KB: latency only)
+// The first two are HBM-bound: the join moves 4 (skip) + 2..4 (residual) + 6 (master + mirror) bytes per element once; conv_out reads the C0-wide
 // map (its nine taps overlap in L1 / L2) and writes 4 channels.
 #include "ops.h"
 
@@ -14,7 +16,7 @@ namespace {
 // residual is added in place): every element is read and written by the same thread.
 __global__ __launch_bounds__(256) void unet_skip_join_kernel(const float* skip, long ld_skip, const void* __restrict__ res, int res_dt,
                                                              long res_frame_b, long res_frame_f, long res_ch, int F, int HW, int C2,
-                                                             float* out32, half_t* out16, long ld_out, int col) {
+                                                             float* out32, half_t* out16, long ld_out, int col, int lo_off) {
     __shared__ float tile[32][65];
     const int n = blockIdx.z, c0 = blockIdx.y * 32, p0 = blockIdx.x * 64;
     const int t = threadIdx.x;
@@ -45,7 +47,16 @@ __global__ __launch_bounds__(256) void unet_skip_join_kernel(const float* skip, 
         h8 h;
 #pragma unroll
         for (int j = 0; j < 8; ++j) h[j] = (half_t)v[j];
-        *(h8*)(out16 + o) = h;
+        if (!lo_off) {
+            *(h8*)(out16 + o) = h;
+        } else {      // split mirror: rows 2 * ld_out wide, the rounding residual rides along (hi + lo == x to ~2^-22)
+            h8 l;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) l[j] = (half_t)(v[j] - (float)h[j]);
+            const size_t o2 = row * 2 * ld_out + col + c0 + cq;
+            *(h8*)(out16 + o2) = h;
+            *(h8*)(out16 + o2 + lo_off) = l;
+        }
     }
 }
 
@@ -90,11 +101,45 @@ __global__ __launch_bounds__(256) void unet_conv_out_kernel(const half_t* __rest
     for (int o = 0; o < Cout; ++o) store_from_f32(out, ((size_t)n * Cout + o) * hw + p, out_dt, acc[o] + bias[o]);
 }
 
+// grid (B), 256 threads.  Row b of out: columns [0, text_dim) the text embedding converted to fp32 (exact for all three dtypes), then
+// for id i the embedding diffusers' Timesteps(dim, flip_sin_to_cos=True, downscale_freq_shift=0) gives time_ids[b][i]: [cos | sin] of
+// id * exp(-ln(10000) k / (dim / 2)).  The sinusoids are computed here, with sincos_kernel's expressions (elementwise.hip), not converted
+// from its output: one launch instead of two, and no [B * n_ids][dim] intermediate.
+__global__ __launch_bounds__(256) void unet_text_time_kernel(const void* __restrict__ text, int text_dt, int text_dim,
+                                                             const float* __restrict__ ids, int n_ids, int dim, float* __restrict__ out,
+                                                             long ld_out) {
+    const int b = blockIdx.x, half_dim = dim / 2;
+    float* row = out + (size_t)b * ld_out;
+    for (int c = threadIdx.x; c < text_dim; c += 256) row[c] = load_as_f32(text, (size_t)b * text_dim + c, text_dt);
+    for (int j = threadIdx.x; j < n_ids * half_dim; j += 256) {
+        const int i = j / half_dim, k = j - i * half_dim;
+        const float tv = ids[(size_t)b * n_ids + i];
+        const float freq = expf(-9.210340371976184f * (float)k / (float)half_dim);
+        const float arg = tv * freq;
+        row[text_dim + i * dim + k] = cosf(arg);
+        row[text_dim + i * dim + half_dim + k] = sinf(arg);
+    }
+}
+
 }  // namespace
 
+int op_unet_text_time(const void* text, int text_dt, int text_dim, const float* ids, int n_ids, int dim, float* out, long ld_out, int B,
+                      hipStream_t s) {
+    CTRL_CHECK(text && ids && out, "unet_text_time: null argument");
+    CTRL_CHECK(text_dt >= DT_F32 && text_dt <= DT_BF16, "unet_text_time: text_embeds must be fp32, fp16 or bf16");
+    CTRL_CHECK(B >= 1 && B <= 65535 && text_dim >= 1 && n_ids >= 1 && dim >= 2 && dim % 2 == 0 && ld_out >= (long)text_dim + (long)n_ids * dim,
+               "unet_text_time: bad sizes (dim even, rows at least text_dim + n_ids * dim wide)");
+    PROF_WORK(0, (double)B * ((text_dt == DT_F32 ? 4.0 : 2.0) * text_dim + 4.0 * n_ids + 4.0 * (text_dim + (double)n_ids * dim)));
+    prof_detail("B%d text%d ids%d dim%d", B, text_dim, n_ids, dim);
+    LAUNCH("unet_text_time", unet_text_time_kernel, dim3((unsigned)B), dim3(256), 0, s, text, text_dt, text_dim, ids, n_ids, dim, out, ld_out);
+    return 0;
+}
+
 int op_unet_skip_join(const float* skip, long ld_skip, const void* res, int res_dt, int res_5d, int B, int F, int HW, int C2, float* out32,
-                      half_t* out16, long ld_out, int col, hipStream_t s) {
+                      half_t* out16, long ld_out, int col, hipStream_t s, int lo_off) {
     CTRL_CHECK(skip && out32, "unet_skip_join: null argument");
+    CTRL_CHECK(lo_off == 0 || (out16 && lo_off % 8 == 0 && lo_off >= col + C2 && (long)lo_off + col + C2 <= 2 * ld_out),
+               "unet_skip_join: a split mirror's lo half must lie behind the hi columns, inside the 2 * ld_out wide row");
     CTRL_CHECK(B >= 1 && F >= 1 && HW >= 1 && (long)B * F <= 65535, "unet_skip_join: bad sizes (at most 65535 frames)");
     CTRL_CHECK(C2 >= 32 && C2 % 32 == 0 && col >= 0 && col % 8 == 0 && ld_skip % 8 == 0 && ld_out % 8 == 0 && ld_skip >= C2 && ld_out >= col + C2,
                "unet_skip_join: C2 must be a multiple of 32, the column offset and the row strides multiples of 8, the rows wide enough");
@@ -103,10 +148,10 @@ int op_unet_skip_join(const float* skip, long ld_skip, const void* res, int res_
     // residual element (b, f, c, p): (b f) c h w -> ((b F + f) C2 + c) HW + p ; b c f h w -> ((b C2 + c) F + f) HW + p
     const long fb = (long)F * C2 * HW, ff = res_5d ? (long)HW : (long)C2 * HW, ch = res_5d ? (long)F * HW : (long)HW;
     const double n = (double)B * F * HW * C2;
-    PROF_WORK(0, n * (4.0 + (res ? (res_dt == DT_F32 ? 4.0 : 2.0) : 0.0) + 4.0 + (out16 ? 2.0 : 0.0)));
+    PROF_WORK(0, n * (4.0 + (res ? (res_dt == DT_F32 ? 4.0 : 2.0) : 0.0) + 4.0 + (out16 ? (lo_off ? 4.0 : 2.0) : 0.0)));
     prof_detail("N%d HW%d C%d col%d%s", B * F, HW, C2, col, res ? (res_5d ? " res5d" : " res4d") : "");
     LAUNCH("unet_skip_join", unet_skip_join_kernel, dim3((unsigned)((HW + 63) / 64), (unsigned)(C2 / 32), (unsigned)(B * F)), dim3(256), 0, s,
-           skip, ld_skip, res, res_dt, fb, ff, ch, F, HW, C2, out32, out16, ld_out, col);
+           skip, ld_skip, res, res_dt, fb, ff, ch, F, HW, C2, out32, out16, ld_out, col, lo_off);
     return 0;
 }
 

@@ -762,6 +762,53 @@ int ctrl_unet_st_forward(ctrl_unet_st* h, const void* sample, int sample_dtype, 
 int ctrl_op_unet_skip_join(const float* skip, int64_t ld_skip, const void* res, int res_dtype, int res_5d, int B, int F, int HW, int C2,
                            float* out32, void* out16, int64_t ld_out, int col, void* stream);
 
+/* ---- SDXL backbone UNet (diffusers UNet2DConditionModel, addition_embed_type "text_time", linear transformer projections) ---- */
+typedef struct ctrl_unet2d_config {
+    int32_t in_channels;                           /* 4 or 8 (the stem kernel's instantiations) */
+    int32_t out_channels;                          /* 1..4 */
+    int32_t num_levels;                            /* len(block_out_channels), 1..4 */
+    int32_t block_out_channels[4];                 /* multiples of 64 */
+    int32_t layers_per_block;                      /* down blocks hold this many ResNets, up blocks one more */
+    int32_t transformer_layers_per_block[4];       /* per level; the mid block takes the last level's, up block i level (levels-1-i)'s */
+    int32_t num_attention_heads[4];                /* per level; out_channels / heads must be 64 where the level (or the mid block) attends */
+    int32_t cross_attention_dim;
+    int32_t level_has_attn[4];                     /* down block i is CrossAttnDownBlock2D (up block levels-1-i mirrors it) */
+    int32_t addition_time_embed_dim;
+    int32_t projection_class_embeddings_input_dim; /* text_embeds width + n_time_ids * addition_time_embed_dim */
+    float norm_eps;                                /* the ResNets' and conv_norm_out's GroupNorm eps */
+} ctrl_unet2d_config;
+typedef struct ctrl_unet2d ctrl_unet2d;   /* opaque */
+/* parameters: diffusers' keys (conv_in.*, time_embedding.linear_{1,2}.*, add_embedding.linear_{1,2}.*, {down,up}_blocks.{i}.resnets.{j}.*,
+   ....attentions.{j}.{norm,proj_in,proj_out}.*, ....attentions.{j}.transformer_blocks.{k}.*, ....downsamplers.0.conv.*,
+   ....upsamplers.0.conv.*, mid_block.{resnets,attentions}.*, conv_norm_out.*, conv_out.*) */
+int ctrl_unet2d_param_count(const ctrl_unet2d_config* cfg);
+int ctrl_unet2d_param_spec(const ctrl_unet2d_config* cfg, int i, char* name, int name_len, int64_t shape[6], int* ndim);
+int ctrl_unet2d_create(const ctrl_unet2d_config* cfg, const ctrl_tensor_ref* tensors, int n_tensors, void* stream, ctrl_unet2d** out);
+void ctrl_unet2d_destroy(ctrl_unet2d* h);
+/* what plan creation selected, as one text line */
+int ctrl_unet2d_selection(ctrl_unet2d* h, char* buf, int len);
+/* step-invariant cache of the text K / V^T projections of every cross-attention: mode 0 off, 1 keep (this forward fills the plan-owned
+   buffers; the first one of a shape allocates them: not under stream capture), 2 reuse (the projections are skipped) */
+int ctrl_unet2d_set_text_cache(ctrl_unet2d* h, int mode);
+/* sample [B][in_channels][h][w] (CTRL_F32 / F16 / BF16) -> out [B][out_channels][h][w] in the same dtype.  timesteps: fp32 device, 1 or B
+   values; encoder_hidden_states [B][Lk][cross_attention_dim]; text_embeds [B][text_dim] (any of the three dtypes) and time_ids fp32
+   device [B][n_time_ids], with text_dim + n_time_ids * addition_time_embed_dim == projection_class_embeddings_input_dim.
+   down_residuals (host array of n_down_residuals device pointers, may be 0): residual i, b c h w in down_dtype, is added to skip i --
+   skip 0 is conv_in's output, then every down block's layer outputs and its down-sampler's.  mid_residual (may be NULL) likewise, added
+   to the mid block's output.  h and w must be multiples of 2^(num_levels - 1).  The first forward of a larger size allocates the
+   workspace (not under stream capture); every later one is capturable: one stream, no side lanes. */
+int ctrl_unet2d_forward(ctrl_unet2d* h, const void* sample, int sample_dtype, int B, int lat_h, int lat_w, const float* timesteps,
+                        int t_count, const void* encoder_hidden_states, int ehs_dtype, int Lk, const void* text_embeds, int text_dtype,
+                        int text_dim, const float* time_ids, int n_time_ids, const void* const* down_residuals, int n_down_residuals,
+                        int down_dtype, const void* mid_residual, int mid_dtype, void* out, void* stream);
+/* bytes of the plan's forward workspace (the largest forward so far) */
+int64_t ctrl_unet2d_workspace_bytes(ctrl_unet2d* h);
+/* op level (csrc/unet.hip): the operand rows of add_embedding.linear_1.  out fp32 [B][ld_out >= text_dim + n_ids * dim]:
+   columns [0, text_dim) = text_embeds[b] converted to fp32, columns text_dim + i * dim + [0, dim) = the sinusoidal embedding of
+   time_ids[b][i] (flip_sin_to_cos, shift 0: [cos | sin], ctrl_op_timestep_sincos's arithmetic).  dim even. */
+int ctrl_op_unet_text_time(const void* text_embeds, int text_dtype, int text_dim, const float* time_ids, int n_ids, int dim, float* out,
+                           int64_t ld_out, int B, void* stream);
+
 /* ---- Router (model/ctrl_router.py) ---- */
 /* weights_out fp32 device [num_routers + (has_mid?1:0)][E]; wg fp32 device same shape (Linear(1,E).weight[:,0]
  * per router; ignored for equal_weights); mask host int[E] (NULL = all ones). */
