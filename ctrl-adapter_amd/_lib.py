@@ -52,6 +52,29 @@ class TAttnDesc(C.Structure):
                 ("Fl", C.c_int32), ("pad0_", C.c_int32)]
 
 
+class GnDesc(C.Structure):
+    """ctrl_gn_desc: one GroupNorm problem with every argument of the op layer"""
+    _fields_ = [("x", C.c_void_p), ("x_dtype", C.c_int32), ("silu", C.c_int32),
+                ("stats", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("y", C.c_void_p),
+                ("imgs", C.c_int32), ("rows_per_img", C.c_int32), ("C", C.c_int32), ("G", C.c_int32),
+                ("eps", C.c_float), ("lo_off", C.c_int32),
+                ("ldx", C.c_int64), ("ldy", C.c_int64), ("stat_rows", C.c_int64), ("y_img_rows", C.c_int64), ("y_row0", C.c_int64)]
+
+
+class LnDesc(C.Structure):
+    """ctrl_ln_desc: one LayerNorm problem (optionally with the added per-image vector)"""
+    _fields_ = [("x", C.c_void_p), ("x_dtype", C.c_int32), ("M", C.c_int32), ("ldx", C.c_int64),
+                ("addv", C.c_void_p), ("ldv", C.c_int64), ("rows_per_img", C.c_int32), ("vmod", C.c_int32), ("xsum", C.c_void_p),
+                ("gamma", C.c_void_p), ("beta", C.c_void_p), ("y", C.c_void_p), ("ldy", C.c_int64),
+                ("C", C.c_int32), ("eps", C.c_float)]
+
+
+class SmallLin(C.Structure):
+    """ctrl_small_lin: one problem of ctrl_op_linear_small_group"""
+    _fields_ = [("x", C.c_void_p), ("ldx", C.c_int64), ("w", C.c_void_p), ("b", C.c_void_p), ("out", C.c_void_p), ("ldo", C.c_int64),
+                ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("in_silu", C.c_int32), ("out_silu", C.c_int32), ("pad0_", C.c_int32)]
+
+
 class TensorRef(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("dtype", C.c_int32), ("ndim", C.c_int32),
                 ("shape", C.c_int64 * 6)]
@@ -136,11 +159,14 @@ class ClipComm(C.Structure):
 
 
 # every symbol include/ctrl_hip.h declares (tests check the library exports all of them)
-ABI_VERSION = 7       # CTRL_ABI_VERSION of include/ctrl_hip.h
+ABI_VERSION = 8       # CTRL_ABI_VERSION of include/ctrl_hip.h
 EXPORTS = [
     "ctrl_abi_version", "ctrl_last_error", "ctrl_prof_begin", "ctrl_prof_end", "ctrl_prof_count", "ctrl_prof_get",
     "ctrl_prof_launch_count", "ctrl_prof_launch_get",
     "ctrl_op_igemm", "ctrl_op_igemm_pinned", "ctrl_op_igemm_group", "ctrl_igemm_splitk_factor", "ctrl_igemm_splitk_ws_bytes", "ctrl_igemm_splitk_ticket_words", "ctrl_igemm_select", "ctrl_op_ffn", "ctrl_op_ffn_pack_w2", "ctrl_range_check", "ctrl_range_status", "ctrl_igemm_set_order", "ctrl_igemm_set_wide", "ctrl_group_launches", "ctrl_policy_set", "ctrl_policy_get", "ctrl_policy_count", "ctrl_policy_name", "ctrl_igemm_tile_of", "ctrl_op_flash_attn", "ctrl_op_flash_attn_group", "ctrl_attn_set_variant", "ctrl_attn_work_map", "ctrl_op_temporal_attn", "ctrl_op_gn_stats_floats", "ctrl_op_gn_stats", "ctrl_op_gn_apply", "ctrl_op_gn_apply_split", "ctrl_op_gn_fused_applies", "ctrl_op_gn_fused", "ctrl_op_pack_conv_w_dup", "ctrl_op_pack_conv_w_phase",
+    "ctrl_op_gn_stats_group", "ctrl_op_gn_apply_group", "ctrl_op_gn_fused_group", "ctrl_gn_launch_shape", "ctrl_op_layernorm_group",
+    "ctrl_op_layernorm_add", "ctrl_op_add_rowvec_clip", "ctrl_op_upsample2x_nhwc", "ctrl_op_fill_zero_group", "ctrl_op_linear_small_group",
+    "ctrl_op_frameidx_sincos",
     "ctrl_op_layernorm", "ctrl_op_nchw_to_nhwc", "ctrl_op_nhwc_to_nchw", "ctrl_avgpool_nchw",
     "ctrl_op_timestep_sincos", "ctrl_op_linear_small", "ctrl_op_blend", "ctrl_op_add_rowvec",
     "ctrl_op_conv3x3_direct", "ctrl_op_conv3x3_small_mfma", "ctrl_op_pack_conv_w", "ctrl_op_pack_conv_w_direct", "ctrl_op_pack_linear_w",
@@ -268,6 +294,21 @@ def lib():
         _lib.ctrl_rccl_comm_bind.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
         _lib.ctrl_rccl_unique_id.argtypes = [C.c_void_p]
         _lib.ctrl_op_gn_stats_floats.restype = C.c_size_t
+        for nm in ("ctrl_op_gn_stats_group", "ctrl_op_gn_apply_group", "ctrl_op_gn_fused_group", "ctrl_op_layernorm_group",
+                   "ctrl_op_linear_small_group"):
+            getattr(_lib, nm).argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        _lib.ctrl_gn_launch_shape.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        _lib.ctrl_op_layernorm_add.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_void_p]
+        _lib.ctrl_op_add_rowvec_clip.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                 C.c_int, C.c_void_p]
+        _lib.ctrl_op_add_rowvec.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.c_int,
+                                            C.c_int, C.c_void_p]
+        _lib.ctrl_op_linear_small.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                              C.c_int, C.c_int, C.c_void_p]
+        _lib.ctrl_op_upsample2x_nhwc.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        _lib.ctrl_op_fill_zero_group.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        _lib.ctrl_op_frameidx_sincos.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         _lib.ctrl_igemm_splitk_ws_bytes.restype = C.c_int64
         _lib.ctrl_igemm_splitk_ws_bytes.argtypes = [C.c_void_p, C.c_int]
         _lib.ctrl_igemm_splitk_ticket_words.restype = C.c_int64

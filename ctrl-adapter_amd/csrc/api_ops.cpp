@@ -83,6 +83,73 @@ int ctrl_op_layernorm(const void* x, int x_dtype, int64_t ldx, const float* gamm
                       int M, int C, float eps, void* stream) {
     return op_layernorm(x, x_dtype, ldx, gamma, beta, H(y), ldy, M, C, eps, S(stream));
 }
+// the test ABI of the norm and streaming kernels (tests/test_gpu_norm_forms.py, tests/test_gpu_stream_forms.py): every argument of the
+// op layer, the grouped launches, and the launch-shape query -- no logic of their own
+static GnStatsArgs gn_stats_args(const ctrl_gn_desc& d) {
+    return GnStatsArgs{d.x, d.x_dtype, d.stats, d.imgs, d.rows_per_img, d.C, d.G, (long)d.ldx};
+}
+static GnApplyArgs gn_apply_args(const ctrl_gn_desc& d) {
+    return GnApplyArgs{d.x, d.x_dtype, d.stats, d.gamma, d.beta, H(d.y), d.imgs, d.rows_per_img, d.C, d.G, d.eps, d.silu, (long)d.ldy, d.lo_off,
+                       (long)d.stat_rows, (long)d.y_img_rows, (long)d.y_row0, (long)d.ldx};
+}
+int ctrl_op_gn_stats_group(const ctrl_gn_desc* d, int n, void* stream) {
+    CTRL_CHECK(d != nullptr && n >= 1 && n <= kMaxGroup, "gn_stats_group: 1..4 descriptors");
+    GnStatsArgs a[kMaxGroup];
+    for (int i = 0; i < n; ++i) a[i] = gn_stats_args(d[i]);
+    return op_gn_stats_group(a, n, S(stream));
+}
+int ctrl_op_gn_apply_group(const ctrl_gn_desc* d, int n, void* stream) {
+    CTRL_CHECK(d != nullptr && n >= 1 && n <= kMaxGroup, "gn_apply_group: 1..4 descriptors");
+    GnApplyArgs a[kMaxGroup];
+    for (int i = 0; i < n; ++i) a[i] = gn_apply_args(d[i]);
+    return op_gn_apply_group(a, n, S(stream));
+}
+int ctrl_op_gn_fused_group(const ctrl_gn_desc* d, int n, void* stream) {
+    CTRL_CHECK(d != nullptr && n >= 1 && n <= kMaxGroup, "gn_fused_group: 1..4 descriptors");
+    GnApplyArgs a[kMaxGroup];
+    for (int i = 0; i < n; ++i) a[i] = gn_apply_args(d[i]);
+    return op_gn_fused_group(a, n, S(stream));
+}
+int ctrl_gn_launch_shape(int imgs, int rows_per_img, int C, int pass, int* rows_per_block, int* chunks) {
+    CTRL_CHECK(gn_launch_shape(imgs, rows_per_img, C, pass, rows_per_block, chunks), "gn_launch_shape: bad arguments");
+    return 0;
+}
+static LnArgs ln_args(const ctrl_ln_desc& d) {
+    return LnArgs{d.x, d.x_dtype, (long)d.ldx, d.addv, (long)d.ldv, d.rows_per_img, d.vmod, d.xsum, d.gamma, d.beta, H(d.y), (long)d.ldy, d.M, d.C,
+                  d.eps};
+}
+int ctrl_op_layernorm_group(const ctrl_ln_desc* d, int n, void* stream) {
+    CTRL_CHECK(d != nullptr && n >= 1 && n <= kMaxGroup, "layernorm_group: 1..4 descriptors");
+    LnArgs a[kMaxGroup];
+    for (int i = 0; i < n; ++i) a[i] = ln_args(d[i]);
+    return op_layernorm_group(a, n, S(stream));
+}
+int ctrl_op_layernorm_add(const void* x, int x_dtype, int64_t ldx, const float* addv, int64_t ldv, int rows_per_img, int vmod, void* xsum,
+                          const float* gamma, const float* beta, void* y, int64_t ldy, int M, int C, float eps, void* stream) {
+    return op_layernorm_add(x, x_dtype, ldx, addv, ldv, rows_per_img, vmod, xsum, gamma, beta, H(y), ldy, M, C, eps, S(stream));
+}
+int ctrl_op_add_rowvec_clip(const void* x, int x_dtype, const float* v, int64_t ldv, void* y, int y_dtype, int B, int F, int L, int C,
+                            void* stream) {
+    return op_add_rowvec_clip(x, x_dtype, v, ldv, y, y_dtype, B, F, L, C, S(stream));
+}
+int ctrl_op_upsample2x_nhwc(const void* x, void* y, int N, int H, int W, int C, void* stream) {
+    CTRL_CHECK(x && y && N >= 1 && H >= 1 && W >= 1, "upsample2x_nhwc: bad arguments");
+    return op_upsample2x_nhwc(CH(x), H(y), N, H, W, C, S(stream));
+}
+int ctrl_op_fill_zero_group(void* const* p, const size_t* bytes, int n, void* stream) {
+    return op_fill_zero_group(p, bytes, n, S(stream));
+}
+int ctrl_op_linear_small_group(const ctrl_small_lin* p, int count, void* stream) {
+    CTRL_CHECK(p != nullptr && count >= 1 && count <= 4096, "linear_small_group: 1..4096 problems");
+    std::vector<SmallLin> q((size_t)count);
+    for (int i = 0; i < count; ++i)
+        q[i] = SmallLin{p[i].x, (long)p[i].ldx, CH(p[i].w), p[i].b, p[i].out, (long)p[i].ldo, p[i].M, p[i].N, p[i].K, p[i].in_silu, p[i].out_silu};
+    return op_linear_small_group(q.data(), count, S(stream));
+}
+int ctrl_op_frameidx_sincos(float* out, int N, int F, int dim, void* stream) {
+    CTRL_CHECK(out && N >= 1 && F >= 1 && dim >= 2 && dim % 2 == 0, "frameidx_sincos: bad arguments");
+    return op_frameidx_sincos(out, N, F, dim, S(stream));
+}
 int ctrl_op_nchw_to_nhwc(const void* x, int dtype, void* y, int N, int C, int HW, void* stream) {
     return op_nchw_to_nhwc(x, dtype, H(y), N, C, HW, S(stream));
 }

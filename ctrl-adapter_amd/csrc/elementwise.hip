@@ -423,6 +423,8 @@ int op_frameidx_sincos(float* out, int N, int F, int dim, hipStream_t s) {
 }
 int op_linear_small(const float* x, long ldx, const half_t* w, const float* b, float* out, long ldo,
                     int M, int N, int K, int in_silu, int out_silu, hipStream_t s) {
+    CTRL_CHECK(x && w && out, "linear_small: null pointer");
+    CTRL_CHECK(N >= 1, "linear_small: N must be at least 1");
     CTRL_CHECK(K % 8 == 0 && ldx % 4 == 0, "linear_small: K must be a multiple of 8 and ldx of 4");
     CTRL_CHECK(M >= 1 && M <= 4096, "linear_small: M out of range");
     dim3 grid((N + 3) / 4, (M + 7) / 8);
@@ -439,6 +441,7 @@ int op_linear_small_group(const SmallLin* probs, int count, hipStream_t s) {
         for (int i = 0; i < g.count; ++i) {
             const SmallLin& q = probs[base + i];
             bytes += 2.0 * q.N * q.K + 4.0 * q.M * ((double)q.K + q.N);
+            CTRL_CHECK(q.x && q.w && q.out, "linear_small_group: null pointer");
             CTRL_CHECK(q.K % 8 == 0 && q.ldx % 4 == 0 && q.M >= 1 && q.N >= 1, "linear_small_group: K must be a multiple of 8");
             g.p[i] = q;
             g.blk_begin[i] = blocks;
@@ -459,6 +462,8 @@ int op_blend(const void* xs, int xs_dt, const void* xt, int xt_dt, const float* 
     return 0;
 }
 int op_add_rowvec(const void* x, int x_dt, const float* v, long ldv, void* y, int y_dt, size_t M, int C, int rows_per_img, int vmod, hipStream_t s) {
+    CTRL_CHECK(x && v && y, "add_rowvec: null pointer");
+    CTRL_CHECK(rows_per_img >= 1 && vmod >= 1, "add_rowvec: rows_per_img and vmod must be at least 1 (the kernel divides by them)");
     CTRL_CHECK(C % 8 == 0, "add_rowvec: C must be a multiple of 8");
     CTRL_CHECK(x_dt != DT_BF16 && y_dt != DT_BF16, "add_rowvec: fp16 / fp32 only");
     const size_t nch = M * (size_t)(C / 8);
@@ -467,6 +472,8 @@ int op_add_rowvec(const void* x, int x_dt, const float* v, long ldv, void* y, in
     return 0;
 }
 int op_add_rowvec_clip(const void* x, int x_dt, const float* v, long ldv, void* y, int y_dt, int B, int F, int L, int C, hipStream_t s) {
+    CTRL_CHECK(x && v && y, "add_rowvec_clip: null pointer");
+    CTRL_CHECK(B >= 1 && F >= 1 && L >= 1, "add_rowvec_clip: B, F and L must be at least 1 (the kernel divides by them)");
     CTRL_CHECK(C % 8 == 0, "add_rowvec_clip: C must be a multiple of 8");
     CTRL_CHECK(x_dt != DT_BF16 && y_dt != DT_BF16, "add_rowvec_clip: fp16 / fp32 only");
     const size_t nch = (size_t)B * F * L * (size_t)(C / 8);

@@ -403,9 +403,16 @@ static int gn_rows_per_block(int imgs, int rows_per_img, int C, int target_block
     return rpb;
 }
 
+bool gn_launch_shape(int imgs, int rows_per_img, int C, int pass, int* rows_per_block, int* chunks) {
+    if (imgs < 1 || rows_per_img < 1 || C < 8 || C % 8 != 0 || C / 8 > 256 || pass < 0 || pass > 1 || !rows_per_block || !chunks) return false;
+    *rows_per_block = gn_rows_per_block(imgs, rows_per_img, C, pass == 0 ? kGnStatsBlocks : kGnApplyBlocks);
+    *chunks = (rows_per_img + *rows_per_block - 1) / *rows_per_block;
+    return true;
+}
+
 size_t op_gn_stats_floats(int imgs, int rows_per_img, int C, int G) {
     if (imgs < 1 || rows_per_img < 1 || C < 8 || C / 8 > 256 || G < 1) return 0;
-    const int rows_per_block = gn_rows_per_block(imgs, rows_per_img, C, 768);
+    const int rows_per_block = gn_rows_per_block(imgs, rows_per_img, C, kGnStatsBlocks);
     const int chunks = (rows_per_img + rows_per_block - 1) / rows_per_block;
     return (size_t)imgs * G * 2 + imgs + (chunks > 1 ? (size_t)imgs * chunks * G * 2 : 0);
 }
@@ -445,8 +452,8 @@ int op_gn_stats_group(const GnStatsArgs* a, int n, hipStream_t s) {
     const long ldx = a[0].ldx > 0 ? a[0].ldx : C;
     CTRL_CHECK(ldx >= C && ldx % 8 == 0, "gn_stats: the row stride of x must be a multiple of 8, at least C");
     // fewer, fatter workgroups than the apply pass: the last workgroup of an image adds all its chunks serially
-    const int rows_per_block = gn_rows_per_block(imgs, rows_per_img, C, 768);
-    const int chunks = (rows_per_img + rows_per_block - 1) / rows_per_block;
+    int rows_per_block = 0, chunks = 0;
+    CTRL_CHECK(gn_launch_shape(imgs, rows_per_img, C, 0, &rows_per_block, &chunks), "gn_stats: bad shape");
     PROF_WORK(0, n * (x_dtype == DT_F32 ? 4.0 : 2.0) * imgs * rows_per_img * C);
     if (n > 1) prof_detail("x%d", n);
     const size_t lds = (size_t)(256 / (C / 8)) * 2 * C * sizeof(float);
@@ -496,8 +503,8 @@ int op_gn_apply_group(const GnApplyArgs* a, int n, hipStream_t s) {
     if (y_img_rows <= 0) y_img_rows = rows_per_img;
     CTRL_CHECK(y_row0 >= 0 && y_row0 + rows_per_img <= y_img_rows, "gn_apply: bad output image layout");
     CTRL_CHECK(ldy % 8 == 0 && lo_off % 8 == 0 && (lo_off == 0 || (lo_off >= C && lo_off + C <= ldy)), "gn_apply: bad split layout");
-    const int rows_per_block = gn_rows_per_block(imgs, rows_per_img, C, 2048);
-    const int chunks = (rows_per_img + rows_per_block - 1) / rows_per_block;
+    int rows_per_block = 0, chunks = 0;
+    CTRL_CHECK(gn_launch_shape(imgs, rows_per_img, C, 1, &rows_per_block, &chunks), "gn_apply: bad shape");
     CTRL_CHECK(x_dtype == DT_F16 || x_dtype == DT_F32, "gn_apply: input must be fp16 or fp32");
     PROF_WORK(0, n * ((x_dtype == DT_F32 ? 6.0 : 4.0) + (lo_off ? 2.0 : 0.0)) * imgs * rows_per_img * C);
     if (n > 1) prof_detail("x%d", n);

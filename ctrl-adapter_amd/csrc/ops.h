@@ -184,6 +184,11 @@ int op_temporal_attn(const TAttnArgs& a, hipStream_t s);
 // `stats` holds op_gn_stats_floats(...) floats (results first, then tickets and per-workgroup partials) and must have
 // been zeroed once (the kernel leaves its tickets zero again).
 size_t op_gn_stats_floats(int imgs, int rows_per_img, int C, int G);
+// launch shape of the two GroupNorm passes: the launchers aim for about this many workgroups in total (the statistics pass fewer and
+// fatter: the last workgroup of an image adds all its chunks).  gn_launch_shape(pass 0 = statistics, 1 = apply) gives rows per
+// workgroup and workgroups (chunks) per image exactly as op_gn_stats_group / op_gn_apply_group launch them; host only, false = bad shape
+constexpr int kGnStatsBlocks = 768, kGnApplyBlocks = 2048;
+bool gn_launch_shape(int imgs, int rows_per_img, int C, int pass, int* rows_per_block, int* chunks);
 // ldx: elements between the rows of x (0 = C; larger: x is a column range of wider rows)
 int op_gn_stats(const void* x, int x_dtype, float* stats, int imgs, int rows_per_img, int C, int G, hipStream_t s, long ldx = 0);
 // y = (x-mean)*rstd*gamma+beta (optionally SiLU); x,y [imgs*rows][C]

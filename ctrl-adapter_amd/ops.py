@@ -342,6 +342,112 @@ def layernorm(x, gamma, beta, eps=1e-5):
     return y
 
 
+# ---- the test ABI of the norm and streaming kernels (tests/norm_forms.py, tests/test_gpu_stream_forms.py): thin, every argument ----
+def gn_desc(x, imgs, rows_per_img, Cc, G, stats=None, gamma=None, beta=None, y=None, eps=1e-5, silu=False, ldx=0, ldy=0, lo_off=0,
+            stat_rows=0, y_img_rows=0, y_row0=0):
+    """ctrl_gn_desc over views the caller keeps alive (x may be a column range of wider rows: pass its row stride as ldx)"""
+    d = L.GnDesc()
+    d.x = x.data_ptr(); d.x_dtype = L.dtype_code(x.dtype); d.silu = int(silu)
+    d.stats = stats.data_ptr() if stats is not None else 0
+    d.gamma = gamma.data_ptr() if gamma is not None else 0
+    d.beta = beta.data_ptr() if beta is not None else 0
+    d.y = y.data_ptr() if y is not None else 0
+    d.imgs = imgs; d.rows_per_img = rows_per_img; d.C = Cc; d.G = G; d.eps = eps; d.lo_off = lo_off
+    d.ldx = ldx; d.ldy = ldy; d.stat_rows = stat_rows; d.y_img_rows = y_img_rows; d.y_row0 = y_row0
+    return d
+
+
+def _group(fn, cls, descs):
+    arr = (cls * len(descs))(*descs)
+    L.check(fn(arr, len(descs), L.cur_stream()))
+
+
+def gn_stats_group(descs):
+    _group(L.lib().ctrl_op_gn_stats_group, L.GnDesc, descs)
+
+
+def gn_apply_group(descs):
+    _group(L.lib().ctrl_op_gn_apply_group, L.GnDesc, descs)
+
+
+def gn_fused_group(descs):
+    _group(L.lib().ctrl_op_gn_fused_group, L.GnDesc, descs)
+
+
+def gn_stats_floats(imgs, rows_per_img, Cc, G):
+    return int(L.lib().ctrl_op_gn_stats_floats(imgs, rows_per_img, Cc, G))
+
+
+def gn_launch_shape(imgs, rows_per_img, Cc, which):
+    """(rows_per_block, chunks) of the statistics (which = 0) / apply (1) launch, as the launchers compute them; host only"""
+    rpb, chunks = C.c_int(), C.c_int()
+    L.check(L.lib().ctrl_gn_launch_shape(imgs, rows_per_img, Cc, which, C.byref(rpb), C.byref(chunks)))
+    return rpb.value, chunks.value
+
+
+def ln_desc(x, gamma, beta, y, M, Cc, ldx, ldy, eps=1e-5, addv=None, ldv=0, rows_per_img=0, vmod=0, xsum=None):
+    d = L.LnDesc()
+    d.x = x.data_ptr(); d.x_dtype = L.dtype_code(x.dtype); d.M = M; d.ldx = ldx
+    d.addv = addv.data_ptr() if addv is not None else 0
+    d.ldv = ldv; d.rows_per_img = rows_per_img; d.vmod = vmod
+    d.xsum = xsum.data_ptr() if xsum is not None else 0
+    d.gamma = gamma.data_ptr(); d.beta = beta.data_ptr(); d.y = y.data_ptr(); d.ldy = ldy; d.C = Cc; d.eps = eps
+    return d
+
+
+def layernorm_group(descs):
+    _group(L.lib().ctrl_op_layernorm_group, L.LnDesc, descs)
+
+
+def layernorm_add(x, addv, ldv, rows_per_img, vmod, xsum, gamma, beta, y, M, Cc, ldx, ldy, eps=1e-5):
+    """xsum = x + addv[(row / rows_per_img) % vmod] (x's dtype, row stride ldx), y = LayerNorm(xsum)"""
+    L.check(L.lib().ctrl_op_layernorm_add(L.ptr(x), L.dtype_code(x.dtype), ldx, L.ptr(addv), ldv, rows_per_img, vmod, L.ptr(xsum), L.ptr(gamma),
+                                          L.ptr(beta), L.ptr(y), ldy, M, Cc, eps, L.cur_stream()))
+
+
+def add_rowvec_clip(x, v, ldv, y, B, F, Lp, Cc):
+    """y[(b f p)] = x + v[(b * Lp + p) % B]; y may be x (in place)"""
+    L.check(L.lib().ctrl_op_add_rowvec_clip(L.ptr(x), L.dtype_code(x.dtype), L.ptr(v), ldv, L.ptr(y), L.dtype_code(y.dtype), B, F, Lp, Cc,
+                                            L.cur_stream()))
+
+
+def upsample2x_nhwc(x):
+    N, H, W, Cc = x.shape
+    y = _f16(N, 2 * H, 2 * W, Cc)
+    L.check(L.lib().ctrl_op_upsample2x_nhwc(L.ptr(x), L.ptr(y), N, H, W, Cc, L.cur_stream()))
+    return y
+
+
+def fill_zero_group(ptrs, sizes):
+    """zero sizes[i] bytes at device address ptrs[i], 1..4 fills in one launch"""
+    n = len(ptrs)
+    pa = (C.c_void_p * n)(*ptrs)
+    sa = (C.c_size_t * n)(*sizes)
+    L.check(L.lib().ctrl_op_fill_zero_group(pa, sa, n, L.cur_stream()))
+
+
+def small_lin(x, ldx, w, b, out, ldo, M, N, K, in_silu=False, out_silu=False):
+    d = L.SmallLin()
+    d.x = x.data_ptr(); d.ldx = ldx; d.w = w.data_ptr(); d.b = b.data_ptr() if b is not None else 0
+    d.out = out.data_ptr(); d.ldo = ldo; d.M = M; d.N = N; d.K = K; d.in_silu = int(in_silu); d.out_silu = int(out_silu)
+    return d
+
+
+def linear_small_group(descs):
+    _group(L.lib().ctrl_op_linear_small_group, L.SmallLin, descs)
+
+
+def linear_small_into(x, ldx, w, b, out, ldo, M, N, K, in_silu=False, out_silu=False):
+    L.check(L.lib().ctrl_op_linear_small(L.ptr(x), ldx, L.ptr(w), L.ptr(b), L.ptr(out), ldo, M, N, K, int(in_silu), int(out_silu),
+                                         L.cur_stream()))
+
+
+def frameidx_sincos(N, F, dim, device="cuda"):
+    out = torch.empty(N, dim, dtype=torch.float32, device=device)
+    L.check(L.lib().ctrl_op_frameidx_sincos(L.ptr(out), N, F, dim, L.cur_stream()))
+    return out
+
+
 def nchw_to_nhwc(x):
     N, Cc, H, W = x.shape
     y = _f16(N, H, W, Cc)

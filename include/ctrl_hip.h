@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define CTRL_ABI_VERSION 7
+#define CTRL_ABI_VERSION 8
 
 /* element types of boundary tensors */
 enum { CTRL_F32 = 0, CTRL_F16 = 1, CTRL_BF16 = 2 };
@@ -255,6 +255,53 @@ int ctrl_op_gn_fused(const void* x, int x_dtype, const float* gamma, const float
                      int imgs, int rows_per_img, int C, int G, float eps, int silu, void* stream);
 int ctrl_op_layernorm(const void* x, int x_dtype, int64_t ldx, const float* gamma, const float* beta, void* y, int64_t ldy,
                       int M, int C, float eps, void* stream);
+/* Test ABI of the norm kernels (tests/norm_forms.py): every argument of the op layer, and its grouped launches.
+   ctrl_gn_desc: one GroupNorm problem.  ldx: elements between the rows of x (0 = C; larger: x is a column range of wider rows);
+   ldy: row stride of y (0 = C); lo_off > 0: the row also carries lo = fp16(v - hi) at column lo_off; stat_rows: rows per image the sums in
+   `stats` span (0 = rows_per_img; larger when they were added over row shards); y_img_rows / y_row0: image i of y starts at row
+   i * y_img_rows + y_row0 (0 = dense).  The statistics pass reads x, x_dtype, stats, imgs, rows_per_img, C, G, ldx; the fused form
+   (ctrl_op_gn_fused_applies) ignores stats, stat_rows, y_img_rows, y_row0 and ldx. */
+typedef struct ctrl_gn_desc {
+    const void* x; int32_t x_dtype; int32_t silu;
+    float* stats; const float* gamma; const float* beta; void* y;
+    int32_t imgs, rows_per_img, C, G;
+    float eps; int32_t lo_off;
+    int64_t ldx, ldy, stat_rows, y_img_rows, y_row0;
+} ctrl_gn_desc;
+/* d[0..n), 1 <= n <= 4: problems that agree in every shape argument share ONE launch (problem = blockIdx.z), others are launched one by
+   one; every member's result is bit for bit what it gets alone */
+int ctrl_op_gn_stats_group(const ctrl_gn_desc* d, int n, void* stream);
+int ctrl_op_gn_apply_group(const ctrl_gn_desc* d, int n, void* stream);
+int ctrl_op_gn_fused_group(const ctrl_gn_desc* d, int n, void* stream);
+/* rows per workgroup and workgroups (chunks) per image of the statistics (pass 0) / apply (pass 1) launch for a shape, as the launchers
+   compute them; launches nothing, needs no device.  0 = filled */
+int ctrl_gn_launch_shape(int imgs, int rows_per_img, int C, int pass, int* rows_per_block, int* chunks);
+/* one LayerNorm problem; addv (optional, fp32 [vmod][ldv]): xsum[m] = x[m] + addv[(m / rows_per_img) % vmod] is written (x's dtype, row
+   stride ldx) and normalised */
+typedef struct ctrl_ln_desc {
+    const void* x; int32_t x_dtype; int32_t M;
+    int64_t ldx;
+    const float* addv; int64_t ldv; int32_t rows_per_img, vmod; void* xsum;
+    const float* gamma; const float* beta; void* y; int64_t ldy;
+    int32_t C; float eps;
+} ctrl_ln_desc;
+int ctrl_op_layernorm_group(const ctrl_ln_desc* d, int n, void* stream);
+int ctrl_op_layernorm_add(const void* x, int x_dtype, int64_t ldx, const float* addv, int64_t ldv, int rows_per_img, int vmod, void* xsum,
+                          const float* gamma, const float* beta, void* y, int64_t ldy, int M, int C, float eps, void* stream);
+/* Test ABI of the small streaming kernels (tests/test_gpu_stream_forms.py).  add_rowvec_clip: rows (clip b, frame, pixel p) of x get
+   v[(b * L + p) % B] added; upsample2x_nhwc: nearest x2 of an fp16 NHWC map; fill_zero_group: 1..4 zero fills of any alignment and size in
+   one launch; linear_small_group: `count` independent ctrl_op_linear_small problems, 40 per launch; frameidx_sincos: ctrl_op_timestep_sincos
+   with t[n] = n % F */
+int ctrl_op_add_rowvec_clip(const void* x, int x_dtype, const float* v, int64_t ldv, void* y, int y_dtype, int B, int F, int L, int C,
+                            void* stream);
+int ctrl_op_upsample2x_nhwc(const void* x, void* y, int N, int H, int W, int C, void* stream);
+int ctrl_op_fill_zero_group(void* const* p, const size_t* bytes, int n, void* stream);
+typedef struct ctrl_small_lin {
+    const float* x; int64_t ldx; const void* w; const float* b; float* out; int64_t ldo;
+    int32_t M, N, K, in_silu, out_silu, pad0_;
+} ctrl_small_lin;
+int ctrl_op_linear_small_group(const ctrl_small_lin* p, int count, void* stream);
+int ctrl_op_frameidx_sincos(float* out, int N, int F, int dim, void* stream);
 int ctrl_op_nchw_to_nhwc(const void* x, int dtype, void* y, int N, int C, int HW, void* stream);
 int ctrl_op_nhwc_to_nchw(const void* x, void* y, int dtype, int N, int C, int HW, float scale, void* stream);
 int ctrl_avgpool_nchw(const void* x, void* y, int dtype, int NC, int Hin, int Win, int Hout, int Wout, void* stream);

@@ -23,7 +23,11 @@ def test_library_exports_every_declared_symbol():
             "ctrl_igemm_select"} <= declared
     # the grouped attention launch, reached outside a plan only through this entry (tests/test_gpu_attn_forms.py)
     assert "ctrl_op_flash_attn_group" in declared
-    assert lib.ctrl_abi_version() == _lib.ABI_VERSION == 7
+    # the test ABI of the norm and streaming kernels (tests/norm_forms.py, tests/test_gpu_norm_forms.py, tests/test_gpu_stream_forms.py)
+    assert {"ctrl_op_gn_stats_group", "ctrl_op_gn_apply_group", "ctrl_op_gn_fused_group", "ctrl_gn_launch_shape", "ctrl_op_layernorm_group",
+            "ctrl_op_layernorm_add", "ctrl_op_add_rowvec_clip", "ctrl_op_upsample2x_nhwc", "ctrl_op_fill_zero_group",
+            "ctrl_op_linear_small_group", "ctrl_op_frameidx_sincos"} <= declared
+    assert lib.ctrl_abi_version() == _lib.ABI_VERSION == 8
 
 
 def test_struct_sizes_match_header():
@@ -31,13 +35,13 @@ def test_struct_sizes_match_header():
     import subprocess
     import tempfile
     from ctrl_adapter_amd import _lib
-    src = '#include "ctrl_hip.h"\n#include <stdio.h>\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(ctrl_igemm_seg), sizeof(ctrl_igemm_desc), sizeof(ctrl_attn_desc), sizeof(ctrl_tattn_desc), sizeof(ctrl_tensor_ref), sizeof(ctrl_controlnet_config), sizeof(ctrl_adapter_config), sizeof(ctrl_clip_comm), sizeof(ctrl_ffn_desc));return 0;}\n'
+    src = '#include "ctrl_hip.h"\n#include <stdio.h>\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(ctrl_igemm_seg), sizeof(ctrl_igemm_desc), sizeof(ctrl_attn_desc), sizeof(ctrl_tattn_desc), sizeof(ctrl_tensor_ref), sizeof(ctrl_controlnet_config), sizeof(ctrl_adapter_config), sizeof(ctrl_clip_comm), sizeof(ctrl_ffn_desc), sizeof(ctrl_gn_desc), sizeof(ctrl_ln_desc), sizeof(ctrl_small_lin));return 0;}\n'
     with tempfile.TemporaryDirectory() as d:
         open(os.path.join(d, "s.c"), "w").write(src)
         subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "s.c"), "-o", os.path.join(d, "s")])
         out = subprocess.check_output([os.path.join(d, "s")]).decode().split()
     got = [ctypes.sizeof(c) for c in (_lib.IGemmSeg, _lib.IGemmDesc, _lib.AttnDesc, _lib.TAttnDesc, _lib.TensorRef,
-                                     _lib.ControlNetConfig, _lib.AdapterConfig, _lib.ClipComm, _lib.FfnDesc)]
+                                     _lib.ControlNetConfig, _lib.AdapterConfig, _lib.ClipComm, _lib.FfnDesc, _lib.GnDesc, _lib.LnDesc, _lib.SmallLin)]
     assert [int(v) for v in out] == got, (out, got)
 
 
