@@ -14,3 +14,4 @@ from .vae_decoder import AutoencoderKL, AutoencoderKLDecoder, DecoderOutput, dec
 from .vae_temporal_decoder import AutoencoderKLTemporalDecoder, decode_svd_latents  # noqa: F401
 from .unet_spatio_temporal import UNetSpatioTemporalConditionModel, UNetSpatioTemporalConditionOutput  # noqa: F401
 from .unet_2d_condition import UNet2DConditionModel, UNet2DConditionOutput  # noqa: F401
+from .unet_i2vgen_xl import I2VGenXLUNet, UNet3DConditionOutput  # noqa: F401

@@ -140,6 +140,11 @@ class UNet2DConfig(C.Structure):
                 ("projection_class_embeddings_input_dim", C.c_int32), ("norm_eps", C.c_float)]
 
 
+class UNetI2VConfig(C.Structure):
+    _fields_ = [("in_channels", C.c_int32), ("out_channels", C.c_int32), ("num_levels", C.c_int32), ("block_out_channels", C.c_int32 * 4),
+                ("layers_per_block", C.c_int32), ("cross_attention_dim", C.c_int32), ("level_has_attn", C.c_int32 * 4)]
+
+
 VAE_DEC_SAMPLE, VAE_DEC_UNIT, VAE_DEC_U8 = 0, 1, 2      # epilogues of ctrl_vae_decoder_forward / ctrl_op_vae_dec_tail
 
 
@@ -193,6 +198,9 @@ EXPORTS = [
     "ctrl_unet_st_forward", "ctrl_op_unet_skip_join",
     "ctrl_unet2d_param_count", "ctrl_unet2d_param_spec", "ctrl_unet2d_create", "ctrl_unet2d_destroy", "ctrl_unet2d_selection",
     "ctrl_unet2d_set_text_cache", "ctrl_unet2d_forward", "ctrl_unet2d_workspace_bytes", "ctrl_op_unet_text_time",
+    "ctrl_unet_i2v_param_count", "ctrl_unet_i2v_param_spec", "ctrl_unet_i2v_create", "ctrl_unet_i2v_destroy", "ctrl_unet_i2v_selection",
+    "ctrl_unet_i2v_set_cond_cache", "ctrl_unet_i2v_forward", "ctrl_unet_i2v_workspace_bytes", "ctrl_op_i2v_latent_encoder",
+    "ctrl_op_adaptive_avgpool_nhwc",
 ]
 
 _lib = None
@@ -212,7 +220,8 @@ def lib():
             fn = getattr(_lib, name)
             if name not in ("ctrl_last_error", "ctrl_policy_get", "ctrl_policy_name", "ctrl_controlnet_destroy", "ctrl_adapter_destroy", "ctrl_rccl_comm_destroy", "ctrl_rccl_comm_bytes_sent",
                             "ctrl_text_encoder_destroy", "ctrl_vision_encoder_destroy", "ctrl_vae_encoder_destroy", "ctrl_vae_decoder_destroy",
-                            "ctrl_vae_tdecoder_destroy", "ctrl_unet_st_destroy", "ctrl_unet2d_destroy", "ctrl_unet2d_workspace_bytes"):
+                            "ctrl_vae_tdecoder_destroy", "ctrl_unet_st_destroy", "ctrl_unet2d_destroy", "ctrl_unet2d_workspace_bytes",
+                            "ctrl_unet_i2v_destroy", "ctrl_unet_i2v_workspace_bytes"):
                 fn.restype = C.c_int
         _lib.ctrl_policy_get.restype = C.c_char_p
         _lib.ctrl_policy_get.argtypes = [C.c_char_p]
@@ -286,6 +295,18 @@ def lib():
                                              C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _lib.ctrl_op_unet_text_time.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int,
                                                 C.c_void_p]
+        _lib.ctrl_unet_i2v_destroy.restype = None
+        _lib.ctrl_unet_i2v_destroy.argtypes = [C.c_void_p]
+        _lib.ctrl_unet_i2v_set_cond_cache.argtypes = [C.c_void_p, C.c_int]
+        _lib.ctrl_unet_i2v_workspace_bytes.restype = C.c_int64
+        _lib.ctrl_unet_i2v_workspace_bytes.argtypes = [C.c_void_p]
+        _lib.ctrl_unet_i2v_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                               C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                               C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.ctrl_op_i2v_latent_encoder.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                    C.c_int, C.c_int, C.c_void_p]
+        _lib.ctrl_op_adaptive_avgpool_nhwc.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                       C.c_int, C.c_void_p]
         _lib.ctrl_rccl_comm_destroy.restype = None
         _lib.ctrl_rccl_comm_destroy.argtypes = [C.c_void_p]
         _lib.ctrl_rccl_comm_bytes_sent.restype = C.c_int64

@@ -259,6 +259,9 @@ int op_conv3x3_direct(const void* in, int in_dtype, int in_nchw, const float* w,
 int op_conv3x3_direct_f32(const void* in, int in_dtype, const float* w, const float* bias, float* out, int N, int Cin, int Cout, int H,
                           int W, hipStream_t s);
 
+// the I2VGen-XL UNet's stem: channels-last fp32 operand rows [N*H*W][8] (sample | encoded image latents) -> fp32 NHWC rows
+int op_conv3x3_rows_f32(const float* in, const float* w, const float* bias, float* out, int N, int Cin, int Cout, int H, int W, hipStream_t s);
+
 // The same convolution on the matrix cores for the channels-last layers with Cin, Cout in {16, 32} (the conditioning embedder's
 // 16 -> 16, 16 -> 32 s2, 32 -> 32): x NHWC fp16, w fp16 [Cout][9][Cin] (op_pack_conv_w), out NHWC fp16 (+ bias, optional SiLU)
 bool op_conv3x3_small_mfma_applies(int Cin, int Cout);
@@ -293,8 +296,24 @@ int op_pack_vec(const void* v, int dtype, float* out, int N, int geglu, hipStrea
 int op_unet_skip_join(const float* skip, long ld_skip, const void* res, int res_dt, int res_5d, int B, int F, int HW, int C2, float* out32,
                       half_t* out16, long ld_out, int col, hipStream_t s, int lo_off = 0);
 // conv_out: x fp16 NHWC [N][H][W][C] (normalised + activated), w fp32 [9][C][Cout] (op_pack_conv_w_direct), Cout <= 4 -> NCHW out_dt
+// layout: where image n lands -- CONV_OUT_NCHW [N][Cout][H][W] (the default), CONV_OUT_NCFHW [N / frames][Cout][frames][H][W] (the
+// I2VGen-XL UNet's b c f h w output, image n = (b, f)), CONV_OUT_ROWS channels-last rows [N * H * W][Cout] (its 16 -> 4 latent stem)
+enum { CONV_OUT_NCHW = 0, CONV_OUT_NCFHW = 1, CONV_OUT_ROWS = 2 };
 int op_unet_conv_out(const half_t* x, const float* w, const float* bias, void* out, int out_dt, int N, int H, int W, int C, int Cout,
-                     hipStream_t s);
+                     hipStream_t s, int layout = CONV_OUT_NCHW, int frames = 1);
+
+// I2VGen-XL's backbone UNet (unet.hip).  image_latents [B][4][F][HW] (fp32 / fp16 / bf16) -> fp32 planes [(b f)][4][HW]
+int op_i2v_frames(const void* x, int dt, float* y, int B, int F, int HW, hipStream_t s);
+// I2VGenXLTransformerTemporalEncoder (dim 4, two heads of 4, FF 4 -> 16 -> 4, erf GELU) over the F <= 32 frames of every pixel, fp32:
+// x rows [(b f) HW][4] (image_latents_proj_in's output) -> columns 4..7 of the conv_in operand rows out8 [(b f) HW][8]; sample
+// (optional, [B][4][F][HW] in sample_dt) -> columns 0..3; keep (optional) [(b f) HW][4]: the encoded latents once more.
+// wts (288 floats): ln g[4] b[4] | to_q [8][4] | to_k [8][4] | to_v [8][4] | to_out [4][8] b[4] | ff.net.0.proj [16][4] b[16] | ff.net.2 [4][16] b[4]
+// precomputed = 1: x already holds encoded latents (a kept forward's `keep`), which are copied
+int op_i2v_latent_encoder(const float* x, const float* wts, const void* sample, int sample_dt, float* out8, float* keep, int B, int F,
+                          int HW, int precomputed, hipStream_t s);
+// adaptive_avg_pool2d of a channels-last map [N][H][W][C] (fp32 | fp16) to [N][OH][OW][C] (fp32 | fp16): windows
+// [floor(i H / OH), ceil((i + 1) H / OH)), summed in fp32; replication where H < OH
+int op_adaptive_avgpool_nhwc(const void* x, int x_dt, void* y, int y_dt, int N, int H, int W, int C, int OH, int OW, hipStream_t s);
 
 // the operand rows of add_embedding.linear_1 of a text_time UNet (SDXL): out fp32 [B][ld_out], columns [0, text_dim) = text_embeds[b]
 // (fp32 / fp16 / bf16) converted, columns text_dim + i * dim + [0, dim) = [cos | sin] of time_ids[b][i] (sincos_kernel's arithmetic)

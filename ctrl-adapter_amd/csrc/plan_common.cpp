@@ -384,8 +384,10 @@ int run_ffn(Ctx& cx, const Lin& ff1, const Lin& ff2, const half_t* xn, int dim, 
 }
 
 int run_basic_tb(Ctx& cx, const BasicTBW& w, const TV& X, const TV& out, int B, int L, const EhsCtx& e, const float* ov_pre,
-                 const PreKV* kv_pre, const half_t* X_ln, int ov_rows) {
-    CTRL_CHECK(e.batch == 1 || e.batch == B || (ov_rows > 0 && ov_pre && e.Lk == 1),
+                 const PreKV* kv_pre, const half_t* X_ln, int ov_rows, int cross_B) {
+    CTRL_CHECK(cross_B == 0 || (cross_B >= 1 && B % cross_B == 0 && e.Lk > 1), "basic_tb: cross_B must divide the image count (several keys)");
+    const int Bx = cross_B ? cross_B : B, Lx = cross_B ? (B / cross_B) * L : L;       // the cross-attention's problems and queries per problem
+    CTRL_CHECK(e.batch == 1 || e.batch == Bx || (ov_rows > 0 && ov_pre && e.Lk == 1),
                "encoder_hidden_states batch must be 1 or equal to the sample batch");
     const size_t mk = cx.mark();
     const int M = B * L, dim = w.dim;
@@ -410,7 +412,7 @@ int run_basic_tb(Ctx& cx, const BasicTBW& w, const TV& X, const TV& out, int B, 
         TV x1 = stream_alloc(cx, (size_t)M * dim, false);
         half_t* xn3 = cx.h((size_t)M * dim);
         TRY(run_self_attn(cx, w.attn1, xn, dim, X, x1, B, L, nullptr, 0, &w.norm2, xn2));
-        TRY(run_cross_attn(cx, w.attn2, w.norm2, x1, dim, x2, B, L, e, kv_pre, xn2, &w.norm3, xn3));
+        TRY(run_cross_attn(cx, w.attn2, w.norm2, x1, dim, x2, Bx, Lx, e, kv_pre, xn2, &w.norm3, xn3));
         TRY(run_ff(cx, w.norm3, w.ff1, w.ff2, x2, dim, out, M, xn3));
     }
     cx.release(mk);

@@ -612,8 +612,10 @@ int project_text_kv(Ctx& cx, const AttnW& w, const EhsCtx& e, PreKV* out);
 // ov_pre (optional, Lk == 1 only): the single-key cross-attention vector computed ahead of time (single_key_vector)
 // X_ln (optional): LayerNorm(norm1)(X) already computed by X's producer (run_linear(..., &w.norm1, X_ln))
 // ov_rows (Lk == 1 with ov_pre): rows that share one row of ov_pre (0 = all rows for a broadcast context, else one image's L)
+// cross_B (Lk > 1; 0 = B): the cross-attention runs as cross_B problems of B * L / cross_B queries -- one context per CLIP whose B / cross_B
+// frames are consecutive images (the I2VGen-XL UNet: nothing is repeated over the frames); e.batch is then 1 or cross_B
 int run_basic_tb(Ctx& cx, const BasicTBW& w, const TV& X, const TV& out, int B, int L, const EhsCtx& e, const float* ov_pre = nullptr,
-                 const PreKV* kv_pre = nullptr, const half_t* X_ln = nullptr, int ov_rows = 0);
+                 const PreKV* kv_pre = nullptr, const half_t* X_ln = nullptr, int ov_rows = 0, int cross_B = 0);
 // [e.batch][dim] fp32 output of a one-key cross-attention (query independent, note N5)
 int single_key_vector(Ctx& cx, const AttnW& w, int dim, const EhsCtx& e, float** out);
 int run_layernorm(Ctx& cx, const Norm& n, const TV& x, half_t* y, int M, int dim);

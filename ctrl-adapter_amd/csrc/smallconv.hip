@@ -12,7 +12,8 @@
 namespace {
 
 // F32_OUT: the output rows in fp32 (the UNet's stem writes its residual stream), else fp16
-template <int CIN, int COT, bool NCHW_IN, bool F32_OUT = false>
+// F32_ROWS_IN (with !NCHW_IN): the channels-last input rows are fp32 (the I2VGen-XL UNet's 8-channel conv_in operand), else fp16
+template <int CIN, int COT, bool NCHW_IN, bool F32_OUT = false, bool F32_ROWS_IN = false>
 __global__ __launch_bounds__(256) void conv3x3_direct_kernel(const void* __restrict__ in, int in_dt,
                                                              const float* __restrict__ w, const float* __restrict__ bias,
                                                              void* __restrict__ out, int N, int Cout, int Hin, int Win,
@@ -39,6 +40,14 @@ __global__ __launch_bounds__(256) void conv3x3_direct_kernel(const void* __restr
 #pragma unroll
             for (int ci = 0; ci < CIN; ++ci)
                 xin[ci] = ok ? load_as_f32(in, (((size_t)n * CIN + ci) * Hin + iy) * Win + ix, in_dt) : 0.f;
+        } else if (F32_ROWS_IN) {
+            const float* ip = (const float*)in + (((size_t)n * Hin + (ok ? iy : 0)) * Win + (ok ? ix : 0)) * CIN;
+#pragma unroll
+            for (int c4 = 0; c4 < CIN / 4; ++c4) {
+                const f4 v = *(const f4*)(ip + c4 * 4);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) xin[c4 * 4 + j] = ok ? v[j] : 0.f;
+            }
         } else {
             const half_t* ip = (const half_t*)in + (((size_t)n * Hin + (ok ? iy : 0)) * Win + (ok ? ix : 0)) * CIN;
 #pragma unroll
@@ -231,6 +240,21 @@ int op_conv3x3_direct_f32(const void* in, int in_dtype, const float* w, const fl
     CTRL_CHECK(Cout % 16 == 0 && ((uintptr_t)out & 15) == 0, "conv3x3_direct_f32: Cout must be a multiple of 16, out 16-byte aligned");
     return Cin == 8 ? launch_stem_f32<8>(in, in_dtype, w, bias, out, N, Cout, H, W, s)
                     : launch_stem_f32<4>(in, in_dtype, w, bias, out, N, Cout, H, W, s);
+}
+
+int op_conv3x3_rows_f32(const float* in, const float* w, const float* bias, float* out, int N, int Cin, int Cout, int H, int W, hipStream_t s) {
+    CTRL_CHECK(Cin == 8, "conv3x3_rows_f32: Cin must be 8 (the I2VGen-XL UNet's stem)");
+    CTRL_CHECK(Cout % 16 == 0 && (((uintptr_t)out | (uintptr_t)in) & 15) == 0, "conv3x3_rows_f32: Cout must be a multiple of 16, in / out 16-byte aligned");
+    const size_t npix = (size_t)N * H * W;
+    PROF_WORK(0, (double)npix * (4.0 * Cin + 4.0 * Cout));
+    prof_detail("N%d %d->%d %dx%d rows f32", N, Cin, Cout, H, W);
+    if (Cout % 32 == 0)
+        LAUNCH("conv3x3_direct", (conv3x3_direct_kernel<8, 32, false, true, true>), dim3((unsigned)((npix + 255) / 256), Cout / 32), dim3(256), 0, s,
+               (const void*)in, DT_F32, w, bias, (void*)out, N, Cout, H, W, H, W, 1, 0);
+    else
+        LAUNCH("conv3x3_direct", (conv3x3_direct_kernel<8, 16, false, true, true>), dim3((unsigned)((npix + 255) / 256), Cout / 16), dim3(256), 0, s,
+               (const void*)in, DT_F32, w, bias, (void*)out, N, Cout, H, W, H, W, 1, 0);
+    return 0;
 }
 
 bool op_conv3x3_small_mfma_applies(int Cin, int Cout) { return (Cin == 16 || Cin == 32) && (Cout == 16 || Cout == 32); }

@@ -856,6 +856,58 @@ int64_t ctrl_unet2d_workspace_bytes(ctrl_unet2d* h);
 int ctrl_op_unet_text_time(const void* text_embeds, int text_dtype, int text_dim, const float* time_ids, int n_ids, int dim, float* out,
                            int64_t ld_out, int B, void* stream);
 
+/* ---- I2VGen-XL backbone UNet (I2VGenXLUNet with the reference's two ControlNet-residual kwargs; diffusers' 3D blocks) ---- */
+typedef struct ctrl_unet_i2v_config {
+    int32_t in_channels;                           /* 4 */
+    int32_t out_channels;                          /* 1..4 */
+    int32_t num_levels;                            /* len(block_out_channels), 1..4 */
+    int32_t block_out_channels[4];                 /* multiples of 64: every transformer of a level has out_channels / 64 heads of 64 */
+    int32_t layers_per_block;                      /* down blocks hold this many layers, up blocks one more */
+    int32_t cross_attention_dim;                   /* a multiple of 32 */
+    int32_t level_has_attn[4];                     /* down block i is CrossAttnDownBlock3D (up block levels-1-i mirrors it) */
+} ctrl_unet_i2v_config;
+typedef struct ctrl_unet_i2v ctrl_unet_i2v;   /* opaque */
+/* parameters: the reference's keys (conv_in.*, transformer_in.*, image_latents_proj_in.{0,2,4}.*, image_latents_temporal_encoder.*,
+   image_latents_context_embedding.{0,3,5}.*, time_embedding.linear_{1,2}.*, context_embedding.{0,2}.*, fps_embedding.{0,2}.*,
+   {down,up}_blocks.{i}.{resnets,temp_convs,attentions,temp_attentions}.{j}.*, ....downsamplers.0.conv.*, ....upsamplers.0.conv.*,
+   mid_block.*, conv_norm_out.*, conv_out.*) */
+int ctrl_unet_i2v_param_count(const ctrl_unet_i2v_config* cfg);
+int ctrl_unet_i2v_param_spec(const ctrl_unet_i2v_config* cfg, int i, char* name, int name_len, int64_t shape[6], int* ndim);
+int ctrl_unet_i2v_create(const ctrl_unet_i2v_config* cfg, const ctrl_tensor_ref* tensors, int n_tensors, void* stream, ctrl_unet_i2v** out);
+void ctrl_unet_i2v_destroy(ctrl_unet_i2v* h);
+/* what plan creation selected, as one text line */
+int ctrl_unet_i2v_selection(ctrl_unet_i2v* h, char* buf, int len);
+/* step-invariant cache of everything that depends on encoder_hidden_states, image_latents and image_embeddings only -- the context
+   matrix's K / V^T projections of every cross-attention and the four encoded latent channels: mode 0 off, 1 keep (this forward fills
+   the plan-owned buffers; the first one of a shape allocates them: not under stream capture), 2 reuse (the stems and the projections
+   are skipped; the three condition inputs are not read) */
+int ctrl_unet_i2v_set_cond_cache(ctrl_unet_i2v* h, int mode);
+/* sample [B][in_channels][F][h][w] (CTRL_F32 / F16 / BF16) -> out [B][out_channels][F][h][w] in the same dtype.  timesteps and fps: fp32
+   device, 1 or B values each; image_latents [B][4][F][h][w], image_embeddings [B][cross_attention_dim], encoder_hidden_states
+   [B][text_len][cross_attention_dim], each in any of the three dtypes.  down_residuals (host array of n_down_residuals device pointers,
+   may be 0): residual i is added to skip i -- skip 0 is transformer_in's output, then every down block's layer outputs and its
+   down-sampler's -- all in one dtype and one layout: (b f) c h w (down_5d = 0) or b c f h w (down_5d = 1).  mid_residual (may be NULL)
+   likewise, added to the mid block's output.  h and w must be multiples of 2^(num_levels - 1), F <= 32.  The first forward of a larger
+   size allocates the workspace (not under stream capture); every later one is capturable: one stream, no side lanes. */
+int ctrl_unet_i2v_forward(ctrl_unet_i2v* h, const void* sample, int sample_dtype, int B, int F, int lat_h, int lat_w, const float* timesteps,
+                          int t_count, const float* fps, int fps_count, const void* image_latents, int latents_dtype,
+                          const void* image_embeddings, int embeddings_dtype, const void* encoder_hidden_states, int ehs_dtype, int text_len,
+                          const void* const* down_residuals, int n_down_residuals, int down_dtype, int down_5d, const void* mid_residual,
+                          int mid_dtype, int mid_5d, void* out, void* stream);
+/* bytes of the plan's forward workspace (the largest forward so far) */
+int64_t ctrl_unet_i2v_workspace_bytes(ctrl_unet_i2v* h);
+/* op level (csrc/unet.hip): I2VGenXLTransformerTemporalEncoder with dim 4 (LayerNorm, two heads of 4 over the F <= 32 frames of a pixel,
+   to_out + residual, feed-forward 4 -> 16 -> 4 with erf GELU + residual), fp32 throughout, one launch.  x fp32 rows [(b f) HW][4] ->
+   columns 4..7 of out8, fp32 rows [(b f) HW][8]; sample (may be NULL) [B][4][F][HW] in sample_dtype -> columns 0..3, converted once; keep
+   (may be NULL) fp32 [(b f) HW][4] receives the encoded rows once more.  weights: 288 floats, norm1 weight[4] bias[4] | to_q [8][4] |
+   to_k [8][4] | to_v [8][4] | to_out.0 weight [4][8] bias[4] | ff.net.0.proj weight [16][4] bias[16] | ff.net.2 weight [4][16] bias[4].
+   precomputed = 1: x already holds encoded rows, which are copied (weights may be NULL). */
+int ctrl_op_i2v_latent_encoder(const float* x, const float* weights, const void* sample, int sample_dtype, float* out8, float* keep, int B,
+                               int F, int HW, int precomputed, void* stream);
+/* op level (csrc/unet.hip): adaptive_avg_pool2d of a channels-last map x [N][H][W][C] to y [N][OH][OW][C] (each CTRL_F32 or CTRL_F16):
+   output (i, j) is the mean over rows [floor(i H / OH), ceil((i + 1) H / OH)) and the like columns, summed in fp32 */
+int ctrl_op_adaptive_avgpool_nhwc(const void* x, int x_dtype, void* y, int y_dtype, int N, int H, int W, int C, int OH, int OW, void* stream);
+
 /* ---- Router (model/ctrl_router.py) ---- */
 /* weights_out fp32 device [num_routers + (has_mid?1:0)][E]; wg fp32 device same shape (Linear(1,E).weight[:,0]
  * per router; ignored for equal_weights); mask host int[E] (NULL = all ones). */
