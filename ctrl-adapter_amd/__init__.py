@@ -15,3 +15,5 @@ from .vae_temporal_decoder import AutoencoderKLTemporalDecoder, decode_svd_laten
 from .unet_spatio_temporal import UNetSpatioTemporalConditionModel, UNetSpatioTemporalConditionOutput  # noqa: F401
 from .unet_2d_condition import UNet2DConditionModel, UNet2DConditionOutput  # noqa: F401
 from .unet_i2vgen_xl import I2VGenXLUNet, UNet3DConditionOutput  # noqa: F401
+from .schedulers import DDIMScheduler, EulerDiscreteScheduler, SchedulerOutput  # noqa: F401
+from .denoise import DenoiseLoop, denoise_svd  # noqa: F401

@@ -145,6 +145,19 @@ class UNetI2VConfig(C.Structure):
                 ("layers_per_block", C.c_int32), ("cross_attention_dim", C.c_int32), ("level_has_attn", C.c_int32 * 4)]
 
 
+class SamplerDesc(C.Structure):
+    """ctrl_sampler_desc: the latents, the model output and the model inputs of one sampler launch"""
+    _fields_ = [("x", C.c_void_p), ("prev", C.c_void_p), ("model_out", C.c_void_p), ("g", C.c_void_p), ("unet_in", C.c_void_p),
+                ("concat", C.c_void_p), ("cn_in", C.c_void_p),
+                ("x_dtype", C.c_int32), ("prev_dtype", C.c_int32), ("mo_dtype", C.c_int32), ("unet_dtype", C.c_int32),
+                ("concat_dtype", C.c_int32), ("cn_dtype", C.c_int32),
+                ("outer", C.c_int32), ("C", C.c_int32), ("inner", C.c_int32), ("C2", C.c_int32), ("R", C.c_int32),
+                ("cn_frames", C.c_int32), ("g_count", C.c_int32), ("g_inner", C.c_int32), ("g_scalar", C.c_float), ("pad0_", C.c_int32)]
+
+
+SAMPLER_ROW = 8       # CTRL_SAMPLER_ROW: c_in, A, B, t_model, t_aux0, t_aux1, 0, 0
+
+
 VAE_DEC_SAMPLE, VAE_DEC_UNIT, VAE_DEC_U8 = 0, 1, 2      # epilogues of ctrl_vae_decoder_forward / ctrl_op_vae_dec_tail
 
 
@@ -201,6 +214,8 @@ EXPORTS = [
     "ctrl_unet_i2v_param_count", "ctrl_unet_i2v_param_spec", "ctrl_unet_i2v_create", "ctrl_unet_i2v_destroy", "ctrl_unet_i2v_selection",
     "ctrl_unet_i2v_set_cond_cache", "ctrl_unet_i2v_forward", "ctrl_unet_i2v_workspace_bytes", "ctrl_op_i2v_latent_encoder",
     "ctrl_op_adaptive_avgpool_nhwc",
+    "ctrl_sampler_create", "ctrl_sampler_destroy", "ctrl_sampler_reset", "ctrl_sampler_scalars", "ctrl_sampler_model_input",
+    "ctrl_sampler_step", "ctrl_op_sampler_reset", "ctrl_op_sampler_model_input", "ctrl_op_sampler_step", "ctrl_op_sampler_launch_shape",
 ]
 
 _lib = None
@@ -221,7 +236,7 @@ def lib():
             if name not in ("ctrl_last_error", "ctrl_policy_get", "ctrl_policy_name", "ctrl_controlnet_destroy", "ctrl_adapter_destroy", "ctrl_rccl_comm_destroy", "ctrl_rccl_comm_bytes_sent",
                             "ctrl_text_encoder_destroy", "ctrl_vision_encoder_destroy", "ctrl_vae_encoder_destroy", "ctrl_vae_decoder_destroy",
                             "ctrl_vae_tdecoder_destroy", "ctrl_unet_st_destroy", "ctrl_unet2d_destroy", "ctrl_unet2d_workspace_bytes",
-                            "ctrl_unet_i2v_destroy", "ctrl_unet_i2v_workspace_bytes"):
+                            "ctrl_unet_i2v_destroy", "ctrl_unet_i2v_workspace_bytes", "ctrl_sampler_destroy", "ctrl_sampler_scalars"):
                 fn.restype = C.c_int
         _lib.ctrl_policy_get.restype = C.c_char_p
         _lib.ctrl_policy_get.argtypes = [C.c_char_p]
@@ -307,6 +322,19 @@ def lib():
                                                     C.c_int, C.c_int, C.c_void_p]
         _lib.ctrl_op_adaptive_avgpool_nhwc.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                        C.c_int, C.c_void_p]
+        _lib.ctrl_sampler_create.argtypes = [C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
+        _lib.ctrl_sampler_destroy.restype = None
+        _lib.ctrl_sampler_destroy.argtypes = [C.c_void_p]
+        _lib.ctrl_sampler_reset.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.ctrl_sampler_scalars.restype = C.c_void_p
+        _lib.ctrl_sampler_scalars.argtypes = [C.c_void_p]
+        _lib.ctrl_sampler_model_input.argtypes = [C.c_void_p, C.POINTER(SamplerDesc), C.c_int, C.c_void_p]
+        _lib.ctrl_sampler_step.argtypes = [C.c_void_p, C.POINTER(SamplerDesc), C.c_int, C.c_int, C.c_void_p]
+        _lib.ctrl_op_sampler_reset.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.ctrl_op_sampler_model_input.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(SamplerDesc), C.c_int, C.c_void_p]
+        _lib.ctrl_op_sampler_step.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(SamplerDesc), C.c_int, C.c_int, C.c_void_p]
+        _lib.ctrl_op_sampler_launch_shape.argtypes = [C.POINTER(SamplerDesc), C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                      C.POINTER(C.c_int)]
         _lib.ctrl_rccl_comm_destroy.restype = None
         _lib.ctrl_rccl_comm_destroy.argtypes = [C.c_void_p]
         _lib.ctrl_rccl_comm_bytes_sent.restype = C.c_int64

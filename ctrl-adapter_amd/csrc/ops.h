@@ -321,6 +321,20 @@ int op_unet_text_time(const void* text, int text_dt, int text_dim, const float* 
                       hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
+// Samplers (sampler.hip): the per-step glue of a denoise loop as one streaming launch.  See include/ctrl_hip.h: ctrl_sampler_desc.
+//   with_step: prev = A_i x + B_i (u + g (c - u));  with_input: the model's inputs (c_in scaling, CFG replicas, concat, the ControlNet's
+//   sample, the three timestep scalars) of row i (alone) or of row i + 1 from the rounded prev (after a step; skipped past the table).
+//   step_index < 0: i is counter[0]; a launch with a step then advances it by a ticket (counter[1]): the last workgroup to finish.
+// ------------------------------------------------------------------------------------------
+typedef ctrl_sampler_desc SamplerDesc;
+constexpr int kSamplerGridCap = 1024;
+int op_sampler(const float* table, int n_steps, int* counter, float* scalars, const SamplerDesc& d, int step_index, bool with_step,
+               bool with_input, hipStream_t s);
+int op_sampler_reset(int* counter, hipStream_t s);
+// validation + launch shape of the above (host only): workgroups, elements per access (8 | 1)
+int sampler_launch_shape(const SamplerDesc& d, bool with_step, bool with_input, int* blocks, int* vec);
+
+// ------------------------------------------------------------------------------------------
 // Conditioning-image preparation (model/ctrl_helper.py:268-296): Pillow-exact 8-bit Lanczos resize + /255 + NCHW + repeats
 //   src uint8 [F][Hin][Win][3]; h/v bounds int32 [out][2] + weights int32 [out][ks] (null = axis not resampled);
 //   tmp uint8 [F][Hin][W][3] (horizontal pass result); out [cfg][rep*F][3][H][W] in out_dtype

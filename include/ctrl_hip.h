@@ -908,6 +908,53 @@ int ctrl_op_i2v_latent_encoder(const float* x, const float* weights, const void*
    output (i, j) is the mean over rows [floor(i H / OH), ceil((i + 1) H / OH)) and the like columns, summed in fp32 */
 int ctrl_op_adaptive_avgpool_nhwc(const void* x, int x_dtype, void* y, int y_dtype, int N, int H, int W, int C, int OH, int OW, void* stream);
 
+/* ---- Samplers (csrc/sampler.hip, csrc/plan_sampler.cpp): the per-step glue of a denoise loop ---- */
+/* One scheduler step of every supported sampler (Euler, DDIM; eta = 0) is linear in the sample x and the guided model output m:
+   prev = A_i x + B_i m, and the model eats c_i x.  The host computes the table in fp64 and hands it over as fp32 rows of
+   CTRL_SAMPLER_ROW floats, one per step: { c_in, A, B, t_model, t_aux0, t_aux1, 0, 0 }.  The kernels multiply and add, nothing else. */
+#define CTRL_SAMPLER_ROW 8
+typedef struct ctrl_sampler_desc {
+    const void* x;          /* latents, (outer, C, inner) dense, x_dtype */
+    void* prev;             /* step: A x + B mg, same shape, prev_dtype; may be x itself (then prev_dtype == x_dtype) */
+    const void* model_out;  /* step: (R * outer, C, inner) in mo_dtype, the unconditional replica first */
+    const float* g;         /* step, R = 2: guidance per frame, fp32 device [g_count]; NULL = g_scalar */
+    void* unet_in;          /* model input: (R * outer, C + C2, inner) in unet_dtype = round(c_in * latents), R replicas along outer */
+    const void* concat;     /* model input: (R * outer, C2, inner) in concat_dtype, copied behind the C channels (NULL: C2 = 0) */
+    void* cn_in;            /* model input (may be NULL): the scaled, replicated latents once more without the concat, in cn_dtype */
+    int32_t x_dtype, prev_dtype, mo_dtype, unet_dtype, concat_dtype, cn_dtype;
+    int32_t outer, C, inner, C2;
+    int32_t R;              /* 1 | 2 classifier-free-guidance replicas */
+    int32_t cn_frames;      /* 0: cn_in is laid out as the latents; F > 0: inner = F * hw and cn_in is (R * outer * F, C, hw), the
+                               b c f h w -> (b f) c h w rearrange */
+    int32_t g_count, g_inner;   /* element e of the latents takes g[(e / g_inner) % g_count] */
+    float g_scalar;
+    int32_t pad0_;
+} ctrl_sampler_desc;
+typedef struct ctrl_sampler ctrl_sampler;   /* opaque: the device table, the step counter (+ its ticket word) and three scalars */
+/* table_fp32_host: n_steps rows; created on the current device (a synchronous upload) */
+int ctrl_sampler_create(int n_steps, const float* table_fp32_host, ctrl_sampler** out);
+void ctrl_sampler_destroy(ctrl_sampler* h);
+/* step counter = 0, by a one-thread kernel (capturable) */
+int ctrl_sampler_reset(ctrl_sampler* h, void* stream);
+/* fp32 device [3]: t_model, t_aux0, t_aux1 of the row the last model-input pass used -- what the modules' `timesteps` (t_count = 1) read */
+float* ctrl_sampler_scalars(ctrl_sampler* h);
+/* the model's inputs of step `step_index` (>= 0; -1: the device counter, which is not advanced) from d->x; writes the scalars */
+int ctrl_sampler_model_input(ctrl_sampler* h, const ctrl_sampler_desc* d, int step_index, void* stream);
+/* prev = A_i x + B_i (u + g (c - u)) with row i = step_index (>= 0), or i = the device counter (-1), which the last workgroup of the
+   launch to finish then advances.  prepare_next: the same launch writes what ctrl_sampler_model_input would write for step i + 1 from
+   the rounded prev (bit-identical to the two calls; skipped on the last step).  A counter beyond the table makes the launch a no-op. */
+int ctrl_sampler_step(ctrl_sampler* h, const ctrl_sampler_desc* d, int step_index, int prepare_next, void* stream);
+/* op level: the same launches on caller-owned buffers.  table: fp32 device [n_steps][CTRL_SAMPLER_ROW]; counter: int32 device [2]
+   (step, ticket), zero once (ctrl_op_sampler_reset zeroes both); scalars: fp32 device [3] */
+int ctrl_op_sampler_reset(int32_t* counter, void* stream);
+int ctrl_op_sampler_model_input(const float* table, int n_steps, const int32_t* counter, float* scalars, const ctrl_sampler_desc* d,
+                                int step_index, void* stream);
+int ctrl_op_sampler_step(const float* table, int n_steps, int32_t* counter, float* scalars, const ctrl_sampler_desc* d, int step_index,
+                         int prepare_next, void* stream);
+/* how a launch over `d` would run (host only): workgroups of 256 threads, elements per thread and access (8: 16-byte accesses, 1: the
+   scalar path), and the cap on the grid beyond which the grid-stride loop takes further trips */
+int ctrl_op_sampler_launch_shape(const ctrl_sampler_desc* d, int with_step, int with_model_input, int* blocks, int* vec, int* grid_cap);
+
 /* ---- Router (model/ctrl_router.py) ---- */
 /* weights_out fp32 device [num_routers + (has_mid?1:0)][E]; wg fp32 device same shape (Linear(1,E).weight[:,0]
  * per router; ignored for equal_weights); mask host int[E] (NULL = all ones). */
