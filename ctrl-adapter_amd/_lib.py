@@ -155,6 +155,13 @@ class SamplerDesc(C.Structure):
                 ("cn_frames", C.c_int32), ("g_count", C.c_int32), ("g_inner", C.c_int32), ("g_scalar", C.c_float), ("pad0_", C.c_int32)]
 
 
+MERGE_SLOTS = 13      # CTRL_MERGE_SLOTS
+
+
+class MergeSlot(C.Structure):
+    _fields_ = [("inp", C.c_void_p * 8), ("out", C.c_void_p), ("elems", C.c_int64), ("row", C.c_int32), ("pad0_", C.c_int32)]
+
+
 SAMPLER_ROW = 8       # CTRL_SAMPLER_ROW: c_in, A, B, t_model, t_aux0, t_aux1, 0, 0
 
 
@@ -216,6 +223,7 @@ EXPORTS = [
     "ctrl_op_adaptive_avgpool_nhwc",
     "ctrl_sampler_create", "ctrl_sampler_destroy", "ctrl_sampler_reset", "ctrl_sampler_scalars", "ctrl_sampler_model_input",
     "ctrl_sampler_step", "ctrl_op_sampler_reset", "ctrl_op_sampler_model_input", "ctrl_op_sampler_step", "ctrl_op_sampler_launch_shape",
+    "ctrl_op_merge_gather_group", "ctrl_op_merge_gather_launch_shape",
 ]
 
 _lib = None
@@ -335,6 +343,10 @@ def lib():
         _lib.ctrl_op_sampler_step.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(SamplerDesc), C.c_int, C.c_int, C.c_void_p]
         _lib.ctrl_op_sampler_launch_shape.argtypes = [C.POINTER(SamplerDesc), C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                                       C.POINTER(C.c_int)]
+        _mg = [C.POINTER(MergeSlot), C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_int, C.c_int,
+               C.c_int, C.c_int]
+        _lib.ctrl_op_merge_gather_group.argtypes = _mg + [C.c_void_p]
+        _lib.ctrl_op_merge_gather_launch_shape.argtypes = _mg + [C.POINTER(C.c_int)] * 3
         _lib.ctrl_rccl_comm_destroy.restype = None
         _lib.ctrl_rccl_comm_destroy.argtypes = [C.c_void_p]
         _lib.ctrl_rccl_comm_bytes_sent.restype = C.c_int64

@@ -206,6 +206,28 @@ int ctrl_router_merge(const void* const* experts_host, const float* weights_row,
                       void* out, int dtype, size_t n, void* stream) {
     return op_weighted_merge(experts_host, weights_row, widx_host, K, out, dtype, n, S(stream));
 }
+static int merge_slots(const ctrl_merge_slot* p, int n, MergeSlot* q) {
+    CTRL_CHECK(p && n >= 1 && n <= CTRL_MERGE_SLOTS, "merge_gather: 1..13 slots");
+    for (int i = 0; i < n; ++i) {
+        for (int k = 0; k < 8; ++k) q[i].in[k] = p[i].in[k];
+        q[i].out = p[i].out; q[i].elems = (long)p[i].elems; q[i].row = p[i].row;
+    }
+    return 0;
+}
+int ctrl_op_merge_gather_group(const ctrl_merge_slot* slots, int n_slots, const float* w, int R, int E, const int* widx_host, int K,
+                               const int32_t* map, int n_in, int n_out, int in_dtype, int out_dtype, void* stream) {
+    MergeSlot q[CTRL_MERGE_SLOTS];
+    TRY(merge_slots(slots, n_slots, q));
+    return op_merge_gather_group(q, n_slots, w, R, E, widx_host, K, map, n_in, n_out, in_dtype, out_dtype, S(stream));
+}
+int ctrl_op_merge_gather_launch_shape(const ctrl_merge_slot* slots, int n_slots, const float* w, int R, int E, const int* widx_host, int K,
+                                      const int32_t* map, int n_in, int n_out, int in_dtype, int out_dtype, int* blocks, int* vec,
+                                      int* grid_cap) {
+    CTRL_CHECK(blocks && vec && grid_cap, "merge_gather_launch_shape: null argument");
+    MergeSlot q[CTRL_MERGE_SLOTS];
+    TRY(merge_slots(slots, n_slots, q));
+    return merge_gather_launch_shape(q, n_slots, w, R, E, widx_host, K, map, n_in, n_out, in_dtype, out_dtype, blocks, vec, grid_cap);
+}
 int ctrl_prepare_images(const void* src_u8, int F, int Hin, int Win, const int32_t* hbounds, const int32_t* hk, int hks,
                         const int32_t* vbounds, const int32_t* vk, int vks, void* tmp_u8, void* out, int out_dtype,
                         int W, int H, int repeat, int cfg, void* stream) {

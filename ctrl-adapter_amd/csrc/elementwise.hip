@@ -255,17 +255,119 @@ struct MergeArgs {
     int widx[8];
     int K;
 };
+// the expert sum of merge_kernel and merge_gather_kernel: fp32, expert order, one expression so that both contract alike
+__device__ __forceinline__ float merge_sum(const float (&wk)[8], const float (&xk)[8], int K) {
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+        if (k < K) s += wk[k] * xk[k];
+    return s;
+}
 __global__ __launch_bounds__(256) void merge_kernel(MergeArgs m, const float* __restrict__ w, void* __restrict__ out,
                                                     int dt, size_t n) {
     float wk[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) wk[k] = (k < m.K) ? w[m.widx[k]] : 0.f;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        float s = 0.f;
+        float xk[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k)
-            if (k < m.K) s += wk[k] * load_as_f32(m.x[k], i, dt);
-        store_from_f32(out, i, dt, s);
+        for (int k = 0; k < 8; ++k) xk[k] = (k < m.K) ? load_as_f32(m.x[k], i, dt) : 0.f;
+        store_from_f32(out, i, dt, merge_sum(wk, xk, m.K));
+    }
+}
+
+// ---- router merge + key-frame gather + cast of up to 13 slots in one launch ----
+// out[s][j][i] = round(sum_k w[row_s E + widx[k]] in_k[s][map[j]][i]).  The slot table travels in the kernel arguments (the launch
+// records into a graph; the host touches no device memory).  The slots differ 64-fold in size, so work is dealt out by elements: a
+// chunk is 256 threads x U elements of ONE slot, chunk_begin holds the slots' prefix sums, and a workgroup walks the chunks
+// blockIdx.x, + gridDim.x, ... and searches the (uniform) slot of each.  U = 8: 16-byte accesses, a thread's 8 elements lie in one
+// frame (elems % 8 == 0); U = 1: the scalar path.  A map entry outside [0, n_in) reads nothing and writes NaN.
+constexpr int kMergeSlots = 13;
+constexpr int kMergeGridCap = 8192;      // grid_for's cap
+struct MergeGatherArgs {
+    const void* x[kMergeSlots][8];
+    void* out[kMergeSlots];
+    size_t per[kMergeSlots];                   // elements of one frame
+    unsigned chunk_begin[kMergeSlots + 1];
+    int row[kMergeSlots];
+    int widx[8];
+    const float* w;
+    const int* map;
+    int K, E, n_slots, n_in, n_out, in_dt, out_dt;
+};
+typedef unsigned short us8 __attribute__((ext_vector_type(8)));
+template <int U>
+__device__ __forceinline__ void ldu(const void* p, size_t e, int dt, float (&o)[U]) {
+    if constexpr (U == 1) {
+        o[0] = load_as_f32(p, e, dt);
+    } else if (dt == DT_F32) {
+        const f4 a = *(const f4*)((const float*)p + e), b = *(const f4*)((const float*)p + e + 4);
+        o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; o[3] = a[3]; o[4] = b[0]; o[5] = b[1]; o[6] = b[2]; o[7] = b[3];
+    } else if (dt == DT_F16) {
+        const h8 v = *(const h8*)((const half_t*)p + e);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = (float)v[j];
+    } else {
+        const us8 v = *(const us8*)((const u16*)p + e);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = bf16_to_f32(v[j]);
+    }
+}
+template <int U>
+__device__ __forceinline__ void stu(void* p, size_t e, int dt, const float (&v)[U]) {
+    if constexpr (U == 1) {
+        store_from_f32(p, e, dt, v[0]);
+    } else if (dt == DT_F32) {
+        *(f4*)((float*)p + e) = f4{v[0], v[1], v[2], v[3]};
+        *(f4*)((float*)p + e + 4) = f4{v[4], v[5], v[6], v[7]};
+    } else if (dt == DT_F16) {
+        h8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = (half_t)v[j];
+        *(h8*)((half_t*)p + e) = o;
+    } else {
+        us8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = f32_to_bf16(v[j]);
+        *(us8*)((u16*)p + e) = o;
+    }
+}
+template <int U>
+__global__ __launch_bounds__(256) void merge_gather_kernel(MergeGatherArgs a) {
+    const unsigned total = a.chunk_begin[a.n_slots];
+    for (unsigned c = blockIdx.x; c < total; c += gridDim.x) {
+        int s = 0;
+        while (s + 1 < a.n_slots && c >= a.chunk_begin[s + 1]) ++s;
+        const size_t per = a.per[s], pu = per / U;
+        const size_t u = (size_t)(c - a.chunk_begin[s]) * 256 + threadIdx.x;
+        if (u >= pu * (size_t)a.n_out) continue;
+        const size_t j = u / pu, r = (u - j * pu) * U;
+        const int src = a.map ? a.map[j] : (int)j;
+        float o[U];
+        if ((unsigned)src >= (unsigned)a.n_in) {
+#pragma unroll
+            for (int e = 0; e < U; ++e) o[e] = __builtin_nanf("");
+        } else if (!a.w) {
+            ldu<U>(a.x[s][0], (size_t)src * per + r, a.in_dt, o);          // weight 1: a gather and a cast, exact
+        } else {
+            float wk[8], xv[8][U];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                wk[k] = 0.f;
+                if (k < a.K) {
+                    wk[k] = a.w[(size_t)a.row[s] * a.E + a.widx[k]];
+                    ldu<U>(a.x[s][k], (size_t)src * per + r, a.in_dt, xv[k]);
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < U; ++e) {
+                float xk[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) xk[k] = (k < a.K) ? xv[k][e] : 0.f;
+                o[e] = merge_sum(wk, xk, a.K);
+            }
+        }
+        stu<U>(a.out[s], j * per + r, a.out_dt, o);
     }
 }
 
@@ -550,6 +652,73 @@ int op_weighted_merge(const void* const* xs, const float* w, const int* widx, in
     for (int k = 0; k < K; ++k) { m.x[k] = xs[k]; m.widx[k] = widx[k]; }
     m.K = K;
     LAUNCH("merge", merge_kernel, dim3(grid_for(n)), dim3(256), 0, s, m, w, out, dtype, n);
+    return 0;
+}
+namespace {
+// checks + the kernel's argument block; blocks / vec as the launch will run
+int merge_gather_args(const MergeSlot* slots, int n_slots, const float* w, int R, int E, const int* widx, int K, const int* map, int n_in,
+                      int n_out, int in_dt, int out_dt, MergeGatherArgs* a, int* blocks, int* vec) {
+    CTRL_CHECK(slots && n_slots >= 1 && n_slots <= kMergeSlots, "merge_gather: 1..13 slots");
+    CTRL_CHECK(K >= 1 && K <= 8, "merge_gather: 1..8 experts supported");
+    CTRL_CHECK(in_dt >= DT_F32 && in_dt <= DT_BF16 && out_dt >= DT_F32 && out_dt <= DT_BF16, "merge_gather: fp32, fp16 or bf16 tensors");
+    CTRL_CHECK(n_in >= 1 && n_out >= 1, "merge_gather: n_in and n_out must be positive");
+    CTRL_CHECK(map || n_out == n_in, "merge_gather: no map is the identity and needs n_out == n_in");
+    CTRL_CHECK(w || K == 1, "merge_gather: no weights (weight 1) needs K == 1");
+    CTRL_CHECK(!w || (widx && R >= 1 && E >= 1), "merge_gather: weights need widx and the shape [R][E]");
+    *a = MergeGatherArgs{};
+    bool v8 = true;
+    for (int s = 0; s < n_slots; ++s) {
+        const MergeSlot& t = slots[s];
+        CTRL_CHECK(t.elems >= 1 && t.out, "merge_gather: a slot needs an output and a positive frame size");
+        CTRL_CHECK((double)t.elems * n_in < 9.0e18 && (double)t.elems * n_out < 9.0e18, "merge_gather: slot too large");
+        CTRL_CHECK(!w || (t.row >= 0 && t.row < R), "merge_gather: weight row out of range");
+        v8 = v8 && t.elems % 8 == 0 && ((uintptr_t)t.out & 15) == 0;
+        for (int k = 0; k < K; ++k) {
+            CTRL_CHECK(t.in[k] && t.in[k] != t.out, "merge_gather: a slot needs K inputs, none of them the output");
+            v8 = v8 && ((uintptr_t)t.in[k] & 15) == 0;
+            a->x[s][k] = t.in[k];
+        }
+        a->out[s] = t.out;
+        a->per[s] = (size_t)t.elems;
+        a->row[s] = t.row;
+    }
+    const int U = v8 ? 8 : 1;
+    size_t chunks = 0;
+    for (int s = 0; s < n_slots; ++s) {
+        a->chunk_begin[s] = (unsigned)chunks;
+        chunks += ((size_t)slots[s].elems / U * n_out + 255) / 256;
+        CTRL_CHECK(chunks < 0x7fffffffu, "merge_gather: too many elements");
+    }
+    a->chunk_begin[n_slots] = (unsigned)chunks;
+    for (int k = 0; k < K; ++k) {
+        CTRL_CHECK(!w || (widx[k] >= 0 && widx[k] < E), "merge_gather: widx out of range");
+        a->widx[k] = w ? widx[k] : 0;
+    }
+    a->w = w; a->map = map;
+    a->K = K; a->E = E; a->n_slots = n_slots; a->n_in = n_in; a->n_out = n_out; a->in_dt = in_dt; a->out_dt = out_dt;
+    *blocks = (int)std::min<size_t>(chunks, (size_t)kMergeGridCap);
+    *vec = U;
+    return 0;
+}
+}  // namespace
+int merge_gather_launch_shape(const MergeSlot* slots, int n_slots, const float* w, int R, int E, const int* widx, int K, const int* map,
+                              int n_in, int n_out, int in_dt, int out_dt, int* blocks, int* vec, int* grid_cap) {
+    MergeGatherArgs a;
+    *grid_cap = kMergeGridCap;
+    return merge_gather_args(slots, n_slots, w, R, E, widx, K, map, n_in, n_out, in_dt, out_dt, &a, blocks, vec);
+}
+int op_merge_gather_group(const MergeSlot* slots, int n_slots, const float* w, int R, int E, const int* widx, int K, const int* map, int n_in,
+                          int n_out, int in_dt, int out_dt, hipStream_t s) {
+    MergeGatherArgs a;
+    int blocks = 0, U = 0;
+    TRY(merge_gather_args(slots, n_slots, w, R, E, widx, K, map, n_in, n_out, in_dt, out_dt, &a, &blocks, &U));
+    const double es[3] = {4.0, 2.0, 2.0};
+    double elems = 0;
+    for (int i = 0; i < n_slots; ++i) elems += (double)slots[i].elems * n_out;
+    PROF_WORK(w ? 2.0 * K * elems : 0.0, elems * (K * es[in_dt] + es[out_dt]));
+    prof_detail("x%d K%d", n_slots, K);
+    if (U == 8) LAUNCH("merge_gather", merge_gather_kernel<8>, dim3(blocks), dim3(256), 0, s, a);
+    else LAUNCH("merge_gather", merge_gather_kernel<1>, dim3(blocks), dim3(256), 0, s, a);
     return 0;
 }
 int op_router_softmax(const float* wg, const int* mask, float* out, int R, int E, int equal_weights, hipStream_t s) {

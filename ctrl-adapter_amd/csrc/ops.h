@@ -245,6 +245,15 @@ int op_fill_zero_group(void* const* p, const size_t* bytes, int n, hipStream_t s
 // K-way weighted merge of NCHW tensors: out = sum_e w[widx[e]] * x_e   (router merge; weights on device)
 int op_weighted_merge(const void* const* xs_dev, const float* w, const int* widx_dev, int K, void* out, int dtype,
                       size_t n, hipStream_t s);
+// router merge + key-frame gather + cast of up to 13 slots in ONE launch: out[s][j] = sum_k w[row_s E + widx[k]] in_k[s][map[j]], frames of
+// `elems` elements; map (device int32 [n_out], NULL = identity) indexes the n_in input frames; w NULL (K == 1) = weight 1, an exact gather.
+// The slot table travels in the kernel arguments: no host access to device memory, no synchronisation, capturable.
+struct MergeSlot { const void* in[8]; void* out; long elems; int row; };
+int op_merge_gather_group(const MergeSlot* slots, int n_slots, const float* w, int R, int E, const int* widx, int K, const int* map, int n_in,
+                          int n_out, int in_dt, int out_dt, hipStream_t s);
+// how that launch would run: workgroups, elements per thread and access (8 | 1), the grid cap (host only; the same checks)
+int merge_gather_launch_shape(const MergeSlot* slots, int n_slots, const float* w, int R, int E, const int* widx, int K, const int* map,
+                              int n_in, int n_out, int in_dt, int out_dt, int* blocks, int* vec, int* grid_cap);
 // router: weights[r][e] = softmax_e( wg[r][e] (or 0) - 1e6*(1-mask[e]) ),  r in [0,R)
 int op_router_softmax(const float* wg, const int* mask, float* out, int R, int E, int equal_weights, hipStream_t s);
 

@@ -77,3 +77,46 @@ class ControlNetRouter(PretrainedMixin, nn.Module):
         if mid_w is not None and mid_list is not None:
             mid = ops.router_merge([mid_list[k] for k in range(len(act))], mid_w.contiguous(), idx)
         return merged, mid
+
+    @staticmethod
+    def expert_columns(expert_masks, num_frames=None, inference_quirk=True):
+        """(the active experts, the weight column each of them reads) as merge computes them, quirk N6 included: merge_frames' half
+        of the rule (merge keeps its own copy; tests/test_merge_gather_host.py holds the two equal)"""
+        act = [e for e in range(len(expert_masks)) if expert_masks[e]]
+        if not inference_quirk:
+            return act, list(range(len(act)))
+        if num_frames is None or int(num_frames) < 1:
+            raise ValueError("merge_frames(inference_quirk=True) needs num_frames (the pipeline indexes "
+                             "w.repeat_interleave(num_frames)); pass inference_quirk=False for train.py's formula")
+        return act, [e // int(num_frames) for e in act]
+
+    @staticmethod
+    def merge_frames(down_lists, mid_list, down_w, mid_w, expert_masks, frames=None, num_frames=None, inference_quirk=True,
+                     out_dtype=None):
+        """merge, the gather of the key frames and the cast to the adapter's dtype in ONE launch (ops.merge_gather) instead of 13
+        merges over dense frames, an index_select and a .to() each: returns (the 12 down tensors, mid), frames `frames` only.
+
+        frames: an int32 device tensor of frame indices into dim 0 (or a list of ints, uploaded here: not under capture), None: every
+        frame.  down_w fp32 [num_routers, E] and mid_w [E] as ControlNetRouter.forward returns them (views of one [R, E] tensor are
+        passed on without a copy); mid_w / mid_list None: no mid.  out_dtype: default the experts' dtype.  The weight columns are
+        merge's (quirk N6 with inference_quirk=True), and so is the fp32 sum: where out_dtype is the experts' dtype the result is
+        bit-identical to merge followed by index_select."""
+        act, idx = ControlNetRouter.expert_columns(expert_masks, num_frames, inference_quirk)
+        K, Rn = len(act), down_w.shape[0]
+        if len(down_lists) < K:
+            raise ValueError("merge_frames: %d active experts but %d ControlNet outputs" % (K, len(down_lists)))
+        has_mid = mid_w is not None and mid_list is not None
+        # the router's rows in one [R, E] tensor: forward's own (down = w[:n], mid = w[n]) when these are its views, else joined
+        w = None
+        if has_mid and down_w.is_contiguous() and mid_w.is_contiguous() and down_w.dtype == torch.float32 and \
+                mid_w.data_ptr() == down_w.data_ptr() + down_w.numel() * 4:
+            w = torch.as_strided(down_w, (Rn + 1, down_w.shape[1]), (down_w.shape[1], 1))
+        if w is None:
+            w = torch.cat([down_w.float(), mid_w.float().reshape(1, -1)]) if has_mid else down_w.float().contiguous()
+        slots = [[down_lists[k][r] for k in range(K)] for r in range(Rn)]
+        if has_mid:
+            slots.append([mid_list[k] for k in range(K)])
+        if frames is not None and not torch.is_tensor(frames):
+            frames = torch.tensor([int(f) for f in frames], dtype=torch.int32, device=slots[0][0].device)
+        out = ops.merge_gather(slots, w, list(range(len(slots))), idx, frame_map=frames, out_dtype=out_dtype)
+        return out[:Rn], (out[Rn] if has_mid else None)

@@ -540,6 +540,63 @@ def router_merge(experts, weights_row, widx):
     return out
 
 
+def _merge_gather_args(slots, outs, weights, rows, widx, frame_map, n_in):
+    """the C argument list shared by ctrl_op_merge_gather_group and its launch-shape query (everything but the stream / the results)"""
+    n = len(slots)
+    if not 1 <= n <= L.MERGE_SLOTS or len(outs) != n:
+        raise ValueError("merge_gather: 1..%d slots, one output each (got %d slots, %d outputs)" % (L.MERGE_SLOTS, n, len(outs)))
+    K = len(slots[0])
+    if not 1 <= K <= 8 or any(len(s) != K for s in slots):
+        raise ValueError("merge_gather: every slot needs the same 1..8 experts")
+    tab = (L.MergeSlot * n)()
+    n_out = outs[0].shape[0]
+    for i, (xs, o) in enumerate(zip(slots, outs)):
+        x0 = xs[0]
+        for x in xs:
+            if not x.is_cuda or not x.is_contiguous() or x.shape != x0.shape or x.dtype != slots[0][0].dtype or x.shape[0] != n_in:
+                raise ValueError("merge_gather: slot %d needs dense GPU experts of one shape [%d, ...] and one dtype" % (i, n_in))
+        if not o.is_contiguous() or o.shape[0] != n_out or tuple(o.shape[1:]) != tuple(x0.shape[1:]) or o.dtype != outs[0].dtype:
+            raise ValueError("merge_gather: output %d must be a dense [%d, %s] tensor" % (i, n_out, ", ".join(map(str, x0.shape[1:]))))
+        for k, x in enumerate(xs):
+            tab[i].inp[k] = x.data_ptr()
+        tab[i].out, tab[i].elems, tab[i].row = o.data_ptr(), x0[0].numel(), int(rows[i]) if rows is not None else 0
+    if frame_map is not None and (frame_map.dtype != torch.int32 or not frame_map.is_cuda or not frame_map.is_contiguous()
+                                  or frame_map.numel() != n_out):
+        raise ValueError("merge_gather: the map must be a dense int32 GPU tensor of %d frame indices" % n_out)
+    if weights is not None and (weights.dim() != 2 or weights.dtype != torch.float32 or not weights.is_cuda or not weights.is_contiguous()):
+        raise ValueError("merge_gather: the weights must be a dense fp32 GPU tensor [R, E]")
+    R, E = (weights.shape[0], weights.shape[1]) if weights is not None else (0, 0)
+    idx = (C.c_int * K)(*[int(v) for v in widx]) if widx is not None else None
+    return [tab, n, L.ptr(weights), R, E, idx, K, L.ptr(frame_map), n_in, n_out, L.dtype_code(slots[0][0].dtype), L.dtype_code(outs[0].dtype)]
+
+
+def merge_gather(slots, weights=None, rows=None, widx=None, frame_map=None, out_dtype=None, out=None):
+    """Router merge + key-frame gather + cast of up to 13 slots in one launch (ctrl_op_merge_gather_group).
+
+    slots: a list of slots, each the list of its K expert tensors [n_in, ...] (one dtype, one K for all).  weights: fp32 [R, E] (the
+    router's output; None: weight 1, K == 1, an exact gather); rows[s]: the weight row of slot s; widx[k]: the column expert k reads.
+    frame_map: int32 device tensor [n_out] of input-frame indices (None: the identity).  Returns the list of [n_out, ...] tensors in
+    out_dtype (default: the input dtype).  The host reads no device memory: the call records into a graph."""
+    x0 = slots[0][0]
+    n_in = x0.shape[0]
+    n_out = int(frame_map.numel()) if frame_map is not None else n_in
+    odt = out_dtype if out_dtype is not None else x0.dtype
+    if out is None:
+        out = [torch.empty((n_out,) + tuple(xs[0].shape[1:]), dtype=odt, device=x0.device) for xs in slots]
+    args = _merge_gather_args(slots, out, weights, rows, widx, frame_map, n_in)
+    with torch.cuda.device(x0.device):
+        L.check(L.lib().ctrl_op_merge_gather_group(*args, L.cur_stream()))
+    return out
+
+
+def merge_gather_launch_shape(slots, outs, weights=None, rows=None, widx=None, frame_map=None):
+    """(workgroups, elements per thread and access, grid cap) of the merge_gather launch over these tensors (host only)"""
+    b, v, cap = C.c_int(), C.c_int(), C.c_int()
+    args = _merge_gather_args(slots, outs, weights, rows, widx, frame_map, slots[0][0].shape[0])
+    L.check(L.lib().ctrl_op_merge_gather_launch_shape(*args, C.byref(b), C.byref(v), C.byref(cap)))
+    return b.value, v.value, cap.value
+
+
 _profiling = False
 
 

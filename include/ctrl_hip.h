@@ -963,6 +963,30 @@ int ctrl_router_weights(const float* wg, const int* mask_host, float* weights_ou
 /* out = sum_k weights[row*E + widx[k]] * experts[k]  over K active experts, element-wise on n elements */
 int ctrl_router_merge(const void* const* experts_host, const float* weights_row, const int* widx_host, int K,
                       void* out, int dtype, size_t n, void* stream);
+/* Router merge, key-frame gather and cast of up to CTRL_MERGE_SLOTS slots (the 12 down residuals and the mid one) in ONE launch:
+     out[s][j][i] = round_to_out_dtype( sum_{k < K} w[row_s * E + widx[k]] * in[k][s][ map[j] ][i] ),  j < n_out, i < elems_s
+   summed in fp32 in expert order with ctrl_router_merge's expression (where the dtypes agree the result is bit-identical to
+   ctrl_router_merge followed by an index_select).  w: fp32 device [R][E], the router's output, NULL = weight 1 (then K == 1: an exact
+   gather + cast); widx: host int[K]; map: int32 device [n_out] frame indices into the n_in input frames, NULL = the identity
+   (n_out == n_in); an entry outside [0, n_in) yields NaN frames.  in_dtype / out_dtype: CTRL_F32 / CTRL_F16 / CTRL_BF16, independent.
+   The slot table travels in the kernel arguments: the host reads no device memory and does not synchronise, so the launch records
+   into a graph.  Work is dealt out by elements (chunks of 256 threads x vec elements, prefix sums over the slots), 16-byte accesses
+   when every elems_s is a multiple of 8 and every pointer 16-byte aligned, the scalar path otherwise. */
+#define CTRL_MERGE_SLOTS 13
+typedef struct ctrl_merge_slot {
+    const void* in[8];      /* K expert tensors [n_in][elems], in_dtype */
+    void* out;              /* [n_out][elems], out_dtype */
+    int64_t elems;          /* elements of one frame */
+    int32_t row;            /* row of w this slot reads */
+    int32_t pad0_;
+} ctrl_merge_slot;
+int ctrl_op_merge_gather_group(const ctrl_merge_slot* slots, int n_slots, const float* w, int R, int E, const int* widx_host, int K,
+                               const int32_t* map, int n_in, int n_out, int in_dtype, int out_dtype, void* stream);
+/* how that launch would run (host only, the same argument checks): workgroups of 256 threads, elements per thread and access (8 | 1),
+   and the cap on the grid beyond which the grid-stride loop takes further trips */
+int ctrl_op_merge_gather_launch_shape(const ctrl_merge_slot* slots, int n_slots, const float* w, int R, int E, const int* widx_host, int K,
+                                      const int32_t* map, int n_in, int n_out, int in_dtype, int out_dtype, int* blocks, int* vec,
+                                      int* grid_cap);
 
 #ifdef __cplusplus
 }
