@@ -184,17 +184,17 @@ class ClipComm(C.Structure):
 
 
 # every symbol include/ctrl_hip.h declares (tests check the library exports all of them)
-ABI_VERSION = 8       # CTRL_ABI_VERSION of include/ctrl_hip.h
+ABI_VERSION = 9       # CTRL_ABI_VERSION of include/ctrl_hip.h
 EXPORTS = [
     "ctrl_abi_version", "ctrl_last_error", "ctrl_prof_begin", "ctrl_prof_end", "ctrl_prof_count", "ctrl_prof_get",
     "ctrl_prof_launch_count", "ctrl_prof_launch_get",
-    "ctrl_op_igemm", "ctrl_op_igemm_pinned", "ctrl_op_igemm_group", "ctrl_igemm_splitk_factor", "ctrl_igemm_splitk_ws_bytes", "ctrl_igemm_splitk_ticket_words", "ctrl_igemm_select", "ctrl_op_ffn", "ctrl_op_ffn_pack_w2", "ctrl_range_check", "ctrl_range_status", "ctrl_igemm_set_order", "ctrl_igemm_set_wide", "ctrl_group_launches", "ctrl_policy_set", "ctrl_policy_get", "ctrl_policy_count", "ctrl_policy_name", "ctrl_igemm_tile_of", "ctrl_op_flash_attn", "ctrl_op_flash_attn_group", "ctrl_attn_set_variant", "ctrl_attn_work_map", "ctrl_op_temporal_attn", "ctrl_op_gn_stats_floats", "ctrl_op_gn_stats", "ctrl_op_gn_apply", "ctrl_op_gn_apply_split", "ctrl_op_gn_fused_applies", "ctrl_op_gn_fused", "ctrl_op_pack_conv_w_dup", "ctrl_op_pack_conv_w_phase",
+    "ctrl_op_igemm", "ctrl_op_igemm_pinned", "ctrl_op_igemm_group", "ctrl_igemm_splitk_factor", "ctrl_igemm_splitk_ws_bytes", "ctrl_igemm_splitk_ticket_words", "ctrl_igemm_select", "ctrl_op_ffn", "ctrl_op_ffn_group", "ctrl_op_ffn_pack_w2", "ctrl_range_check", "ctrl_range_status", "ctrl_igemm_set_order", "ctrl_igemm_set_wide", "ctrl_group_launches", "ctrl_policy_set", "ctrl_policy_get", "ctrl_policy_count", "ctrl_policy_name", "ctrl_igemm_tile_of", "ctrl_op_flash_attn", "ctrl_op_flash_attn_group", "ctrl_attn_set_variant", "ctrl_attn_work_map", "ctrl_op_temporal_attn", "ctrl_op_gn_stats_floats", "ctrl_op_gn_stats", "ctrl_op_gn_apply", "ctrl_op_gn_apply_split", "ctrl_op_gn_fused_applies", "ctrl_op_gn_fused", "ctrl_op_pack_conv_w_dup", "ctrl_op_pack_conv_w_phase",
     "ctrl_op_gn_stats_group", "ctrl_op_gn_apply_group", "ctrl_op_gn_fused_group", "ctrl_gn_launch_shape", "ctrl_op_layernorm_group",
     "ctrl_op_layernorm_add", "ctrl_op_add_rowvec_clip", "ctrl_op_upsample2x_nhwc", "ctrl_op_fill_zero_group", "ctrl_op_linear_small_group",
     "ctrl_op_frameidx_sincos",
     "ctrl_op_layernorm", "ctrl_op_nchw_to_nhwc", "ctrl_op_nhwc_to_nchw", "ctrl_avgpool_nchw",
     "ctrl_op_timestep_sincos", "ctrl_op_linear_small", "ctrl_op_blend", "ctrl_op_add_rowvec",
-    "ctrl_op_conv3x3_direct", "ctrl_op_conv3x3_small_mfma", "ctrl_op_pack_conv_w", "ctrl_op_pack_conv_w_direct", "ctrl_op_pack_linear_w",
+    "ctrl_op_conv3x3_direct", "ctrl_op_conv3x3_direct_f32", "ctrl_op_conv3x3_rows_f32", "ctrl_op_conv3x3_small_mfma", "ctrl_op_pack_conv_w", "ctrl_op_pack_conv_w_direct", "ctrl_op_pack_linear_w",
     "ctrl_op_pack_vec",
     "ctrl_controlnet_param_count", "ctrl_controlnet_param_spec", "ctrl_controlnet_create",
     "ctrl_controlnet_destroy", "ctrl_controlnet_clone", "ctrl_controlnet_forward",
@@ -375,6 +375,12 @@ def lib():
         _lib.ctrl_igemm_splitk_ticket_words.restype = C.c_int64
         _lib.ctrl_igemm_splitk_ticket_words.argtypes = [C.c_void_p, C.c_int]
         _lib.ctrl_igemm_select.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_int]
+        _lib.ctrl_op_ffn.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.ctrl_op_ffn_group.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        _lib.ctrl_op_conv3x3_direct_f32.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                    C.c_int, C.c_void_p]
+        _lib.ctrl_op_conv3x3_rows_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                  C.c_void_p]
         if _lib.ctrl_abi_version() != ABI_VERSION:
             raise RuntimeError("libctrlhip ABI version mismatch")
     return _lib

@@ -28,6 +28,10 @@ int ctrl_op_ffn(const ctrl_ffn_desc* d, void* stream) {
     CTRL_CHECK(d != nullptr, "ffn: null descriptor");
     return op_ffn_fused_group(d, 1, S(stream));
 }
+int ctrl_op_ffn_group(const ctrl_ffn_desc* d, int n, void* stream) {
+    CTRL_CHECK(d != nullptr, "ffn_group: null descriptor array");
+    return op_ffn_fused_group(d, n, S(stream));
+}
 int ctrl_op_ffn_pack_w2(const void* w2_packed, void* out, int N, int K, void* stream) {
     CTRL_CHECK(w2_packed && out, "ffn_pack_w2: null argument");
     return op_ffn_pack_w2((const half_t*)w2_packed, (half_t*)out, N, K, S(stream));
@@ -175,6 +179,16 @@ int ctrl_op_add_rowvec(const void* x, int x_dtype, const float* v, int64_t ldv, 
 int ctrl_op_conv3x3_direct(const void* in, int in_dtype, int in_nchw, const float* w, const float* bias, void* out,
                            int N, int Cin, int Cout, int Hin, int Win, int stride, int silu, void* stream) {
     return op_conv3x3_direct(in, in_dtype, in_nchw, w, bias, H(out), N, Cin, Cout, Hin, Win, stride, silu, S(stream));
+}
+int ctrl_op_conv3x3_direct_f32(const void* in, int in_dtype, const float* w, const float* bias, void* out, int N, int Cin, int Cout,
+                               int H, int W, void* stream) {
+    CTRL_CHECK(in && w && out && N >= 1 && H >= 1 && W >= 1, "conv3x3_direct_f32: bad arguments");
+    return op_conv3x3_direct_f32(in, in_dtype, w, bias, (float*)out, N, Cin, Cout, H, W, S(stream));
+}
+int ctrl_op_conv3x3_rows_f32(const void* in, const float* w, const float* bias, void* out, int N, int Cin, int Cout, int H, int W,
+                             void* stream) {
+    CTRL_CHECK(in && w && out && N >= 1 && H >= 1 && W >= 1, "conv3x3_rows_f32: bad arguments");
+    return op_conv3x3_rows_f32((const float*)in, w, bias, (float*)out, N, Cin, Cout, H, W, S(stream));
 }
 int ctrl_op_conv3x3_small_mfma(const void* x, const void* w, const float* bias, void* out, int N, int Cin, int Cout, int Hin, int Win,
                                int stride, int silu, void* stream) {

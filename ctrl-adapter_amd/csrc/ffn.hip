@@ -191,6 +191,20 @@ __global__ __launch_bounds__(512, 2) void ffn512_kernel(FfnGroup kargs, int per,
     // GEGLU of k-step KAP (hidden (KAP >> 1) * 16 + 4 fq + 2 (KAP & 1) + {0, 1} of the wave column's 32), token fragment MI: two products,
     // packed fp16, one 4-byte store.  k-step KAP of G2 then reads, per row, chunk (KAP & 1) * 4 + wave column = 8 hidden of that wave column
     float pmax = 0.f;                 // range check of the fp16 hidden activation: branch-free in the loop, one test at the end
+    // ... over the rows that exist: X rows beyond M arrive as zeros, so P there is b1h * gelu(b1g) -- a value no token produced, which must
+    // not raise the flag (the GEMM epilogue masks its check with row < M in the same way).  A lane's token row of fragment mi is
+    // m0 + wm * 64 + mi * 16 + (lane & 15): the rows of a fragment that exist are an EXEC mask for the one v_max3 -- four scalar
+    // pairs, no vector register (which the chunk loop does not have)
+    unsigned long long pm[4];
+    {
+        const int mrem = e.M - m0 - wm * 64;
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi) {
+            const int lim = min(max(mrem - mi * 16, 0), 16);
+            pm[mi] = (unsigned long long)((1u << lim) - 1u) * 0x0001000100010001ull;
+            asm volatile("" : "+s"(pm[mi]));
+        }
+    }
 #define FF_GEGLU(KAP, MI)                                                                                              \
     do {                                                                                                               \
         float p0_ = sacc[MI][2 * ((KAP) >> 1)][2 * ((KAP) & 1)], p1_ = sacc[MI][2 * ((KAP) >> 1)][2 * ((KAP) & 1) + 1];                      \
@@ -202,7 +216,9 @@ __global__ __launch_bounds__(512, 2) void ffn512_kernel(FfnGroup kargs, int per,
         }                                                                                                              \
         /* (in place, one instruction: left to the compiler the maximum chain sinks to the end of the chunk body and keeps every    \
            product alive -- in scratch -- until there) */                                                                  \
-        asm volatile("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(pmax) : "v"(p0_), "v"(p1_));                                \
+        unsigned long long sv_;                                                                                        \
+        asm volatile("s_and_saveexec_b64 %1, %4\n\tv_max3_f32 %0, %0, |%2|, |%3|\n\ts_mov_b64 exec, %1"                 \
+                     : "+v"(pmax), "=&s"(sv_) : "v"(p0_), "v"(p1_), "s"(pm[MI]) : "scc");                              \
         const h2 pk_ = {(half_t)p0_, (half_t)p1_};                                                                      \
         int pwb_ = pw0;                                                                                                \
         asm volatile("" : "+v"(pwb_));                                                                                 \
@@ -317,9 +333,20 @@ static int ffn_check(const FfnArgs& a) {
     CTRL_CHECK((double)e.M * (double)a.ldx * 2.0 < 2147483648.0, "ffn: X beyond 2 GiB");
     CTRL_CHECK(e.nseg == 1 && e.seg[0].fmt == SEG_ROW && e.seg[0].col_begin == 0 && e.seg[0].ncols == ff::D && !e.geglu && !e.rowvec && !e.act &&
                e.res_up != 2 && e.scale2_from == 0, "ffn: one row-major output segment, no GEGLU / per-image vector / activation on the output GEMM");
+    // what the swapped epilogue (igemm_epilogue<.., true, 1>: 16-byte pieces of rows) asks of an implicit GEMM through can_swap(), and the
+    // descriptor fields it would act on that this op does not offer
+    CTRL_CHECK(e.seg[0].out && (e.seg[0].dtype == DT_F16 || e.seg[0].dtype == DT_F32), "ffn: the output must be fp16 or fp32 rows");
+    CTRL_CHECK(e.seg[0].ld >= ff::D && e.seg[0].ld % 8 == 0 && (!e.res || (e.ldres >= ff::D && e.ldres % 8 == 0)) &&
+               (!e.out16 || (e.ld16 >= ff::D && e.ld16 % 8 == 0)) && (!e.blend_mix || (e.ld_blend >= ff::D && e.ld_blend % 8 == 0)),
+               "ffn: the row strides of out / res / out16 / blend_x must be multiples of 8 elements, at least 512");
+    CTRL_CHECK((((uintptr_t)e.seg[0].out | (uintptr_t)e.res | (uintptr_t)e.out16 | (uintptr_t)e.bias | (uintptr_t)(e.blend_mix ? e.blend_x : nullptr)) & 15) == 0,
+               "ffn: out / res / out16 / bias / blend_x must be 16-byte aligned");
+    CTRL_CHECK(e.scale == 1.0f && e.out16_lo_off == 0 && (!e.blend_mix || e.blend_x),
+               "ffn: no output scale, no split mirror; an AlphaBlender fold needs blend_x");
     // the epilogue addresses rows with 32-bit element offsets
     CTRL_CHECK((double)e.M * (double)e.seg[0].ld < 4294967296.0 && (!e.res || (double)e.M * (double)e.ldres < 4294967296.0) &&
-               (!e.out16 || (double)e.M * (double)e.ld16 < 4294967296.0), "ffn: output beyond 2^32 elements");
+               (!e.out16 || (double)e.M * (double)e.ld16 < 4294967296.0) && (!e.blend_mix || (double)e.M * (double)e.ld_blend < 4294967296.0),
+               "ffn: output beyond 2^32 elements");
     return 0;
 }
 

@@ -202,6 +202,9 @@ int op_conv3x3_direct(const void* in, int in_dtype, int in_nchw, const float* w,
                       int N, int Cin, int Cout, int Hin, int Win, int stride, int silu, hipStream_t s) {
     CTRL_CHECK(stride == 1 || stride == 2, "conv3x3_direct: stride must be 1 or 2");
     CTRL_CHECK(Cout % 16 == 0, "conv3x3_direct: Cout must be a multiple of 16");
+    // 16-byte stores of the output rows, 16-byte loads of the channels-last input rows
+    CTRL_CHECK(in && w && out && ((uintptr_t)out & 15) == 0 && (in_nchw || ((uintptr_t)in & 15) == 0),
+               "conv3x3_direct: out (and a channels-last in) must be 16-byte aligned");
     const bool c32 = (Cout % 32) == 0;
 #define DIRECT_CASE(CI, NCHW)                                                                                   \
     if (Cin == CI && (in_nchw != 0) == NCHW) {                                                                  \

@@ -146,27 +146,47 @@ def ffn_pack_w2(w2_packed):
     return out
 
 
-def ffn_fused(x, w1p, b1p, w2pp, b2=None, res=None, out=None, out16=None):
-    """out = res + ((x W1h^T + b1h) * gelu(x W1g^T + b1g)) W2^T + b2 in ONE launch (csrc/ffn.hip): x fp16 [M][512]; w1p / b1p the GEGLU
-    packs of ff.net.0.proj (pack_linear_w / pack_vec with geglu=True), w2pp = ffn_pack_w2(pack_linear_w(W2)); res fp32 or fp16 [M][512];
-    out fp32 or fp16 [M][512] (default fp16), out16 an optional fp16 mirror of an fp32 out"""
-    M, K = x.shape
-    if out is None:
-        out = _f16(M, 512)
+def ffn_desc(x, w1p, b1p, w2pp, out, b2=None, res=None, out16=None, ld=512, ldres=512, ld16=512, blend_mix=None, blend_x=None, ld_blend=512,
+             M=None):
+    """the ctrl_ffn_desc of ffn_fused's arguments (the tensors must stay alive while it is used).  x, out, res, out16 and blend_x may be
+    views into larger buffers: each is addressed from its first element with the row stride given beside it (ld / ldres / ld16 /
+    ld_blend in elements; x rows are always 512 apart)"""
     d = L.FfnDesc()
-    d.X = x.data_ptr(); d.ldx = K; d.W1 = w1p.data_ptr(); d.b1 = b1p.data_ptr(); d.W2p = w2pp.data_ptr()
+    d.X = x.data_ptr(); d.ldx = x.shape[1]; d.W1 = w1p.data_ptr(); d.b1 = b1p.data_ptr(); d.W2p = w2pp.data_ptr()
     o = d.out
-    o.M = M; o.Nout = 512; o.Ktot = 2048; o.Cin = 2048; o.taps = 1; o.scale = 1.0; o.rows_per_img = 1
+    o.M = x.shape[0] if M is None else M; o.Nout = 512; o.Ktot = 2048; o.Cin = 2048; o.taps = 1; o.scale = 1.0; o.rows_per_img = 1
     o.Hin = o.Win = o.Hout = o.Wout = o.stride = o.up = 1
     o.bias = b2.data_ptr() if b2 is not None else None
     o.res = res.data_ptr() if res is not None else None
-    o.ldres = 512
+    o.ldres = ldres
     o.res_f32 = int(res is not None and res.dtype == torch.float32)
     o.out16 = out16.data_ptr() if out16 is not None else None
-    o.ld16 = 512
+    o.ld16 = ld16
+    o.blend_mix = blend_mix.data_ptr() if blend_mix is not None else None
+    o.blend_x = blend_x.data_ptr() if blend_x is not None else None
+    o.ld_blend = ld_blend
+    o.blend_f32 = int(blend_x is not None and blend_x.dtype == torch.float32)
     o.nseg = 1
-    o.seg[0].out = out.data_ptr(); o.seg[0].ld = 512; o.seg[0].col_begin = 0; o.seg[0].ncols = 512
+    o.seg[0].out = out.data_ptr(); o.seg[0].ld = ld; o.seg[0].col_begin = 0; o.seg[0].ncols = 512
     o.seg[0].fmt = SEG_ROW; o.seg[0].dtype = L.dtype_code(out.dtype); o.seg[0].L = 1
+    return d
+
+
+def ffn_group(descs):
+    """1..4 feed-forwards of equal M (ffn_desc) through ctrl_op_ffn_group: ONE launch, the way the plans launch the sibling adapter
+    blocks of a pyramid level; the caller keeps the tensors behind the descriptors alive"""
+    arr = (L.FfnDesc * len(descs))(*descs)
+    L.check(L.lib().ctrl_op_ffn_group(arr, len(descs), L.cur_stream()))
+
+
+def ffn_fused(x, w1p, b1p, w2pp, b2=None, res=None, out=None, out16=None, ld=512, ldres=512, ld16=512):
+    """out = res + ((x W1h^T + b1h) * gelu(x W1g^T + b1g)) W2^T + b2 in ONE launch (csrc/ffn.hip): x fp16 [M][512]; w1p / b1p the GEGLU
+    packs of ff.net.0.proj (pack_linear_w / pack_vec with geglu=True), w2pp = ffn_pack_w2(pack_linear_w(W2)); res fp32 or fp16 [M][512];
+    out fp32 or fp16 [M][512] (default fp16), out16 an optional fp16 mirror of an fp32 out; ld / ldres / ld16: the row strides of out /
+    res / out16 in elements (views into wider buffers)"""
+    if out is None:
+        out = _f16(x.shape[0], 512)
+    d = ffn_desc(x, w1p, b1p, w2pp, out, b2=b2, res=res, out16=out16, ld=ld, ldres=ldres, ld16=ld16)
     L.check(L.lib().ctrl_op_ffn(C.byref(d), L.cur_stream()))
     return out
 
@@ -500,23 +520,46 @@ def add_rowvec(x, v, rows_per_img, vmod):
     return y
 
 
-def conv3x3_direct(x, w_direct, bias, Cout, stride=1, silu=False, nchw=False):
+def conv3x3_direct(x, w_direct, bias, Cout, stride=1, silu=False, nchw=False, out=None):
+    """x NCHW of any dtype (Cin 3 | 4) or NHWC fp16 (Cin 16 | 32), w_direct = pack_conv_w_direct(w) -> fp16 NHWC [N][Ho][Wo][Cout]
+    (`out`: a dense fp16 tensor of that size to write into)"""
     if nchw:
         N, Cin, H, W = x.shape
     else:
         N, H, W, Cin = x.shape
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    out = _f16(N, Ho, Wo, Cout)
+    if out is None:
+        out = _f16(N, Ho, Wo, Cout)
     L.check(L.lib().ctrl_op_conv3x3_direct(L.ptr(x), L.dtype_code(x.dtype), int(nchw), L.ptr(w_direct), L.ptr(bias), L.ptr(out),
                                            N, Cin, Cout, H, W, stride, int(silu), L.cur_stream()))
     return out
 
 
-def conv3x3_small_mfma(x, w_packed, bias, Cout, stride=1, silu=False):
+def conv3x3_direct_f32(x_nchw, w_direct, bias, Cout, out=None):
+    """the backbone UNets' stem: x NCHW [N][Cin][H][W] of any dtype (Cin 4 | 8) -> fp32 rows [N][H][W][Cout] (stride 1, no activation)"""
+    N, Cin, H, W = x_nchw.shape
+    if out is None:
+        out = torch.empty(N, H, W, Cout, dtype=torch.float32, device=x_nchw.device)
+    L.check(L.lib().ctrl_op_conv3x3_direct_f32(L.ptr(x_nchw), L.dtype_code(x_nchw.dtype), L.ptr(w_direct), L.ptr(bias), L.ptr(out), N, Cin, Cout,
+                                               H, W, L.cur_stream()))
+    return out
+
+
+def conv3x3_rows_f32(x_rows, w_direct, bias, Cout, out=None):
+    """the I2VGen-XL UNet's stem: x fp32 channels-last [N][H][W][8] -> fp32 rows [N][H][W][Cout] (stride 1, no activation)"""
+    N, H, W, Cin = x_rows.shape
+    if out is None:
+        out = torch.empty(N, H, W, Cout, dtype=torch.float32, device=x_rows.device)
+    L.check(L.lib().ctrl_op_conv3x3_rows_f32(L.ptr(x_rows), L.ptr(w_direct), L.ptr(bias), L.ptr(out), N, Cin, Cout, H, W, L.cur_stream()))
+    return out
+
+
+def conv3x3_small_mfma(x, w_packed, bias, Cout, stride=1, silu=False, out=None):
     """x NHWC fp16 [N][H][W][Cin] (Cin, Cout in {16, 32}), w_packed = pack_conv_w(w): the MFMA form of the small convolutions"""
     N, H, W, Cin = x.shape
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    out = _f16(N, Ho, Wo, Cout)
+    if out is None:
+        out = _f16(N, Ho, Wo, Cout)
     L.check(L.lib().ctrl_op_conv3x3_small_mfma(L.ptr(x), L.ptr(w_packed), L.ptr(bias), L.ptr(out), N, Cin, Cout, H, W, stride, int(silu),
                                                L.cur_stream()))
     return out

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define CTRL_ABI_VERSION 8
+#define CTRL_ABI_VERSION 9
 
 /* element types of boundary tensors */
 enum { CTRL_F32 = 0, CTRL_F16 = 1, CTRL_BF16 = 2 };
@@ -149,7 +149,11 @@ int ctrl_igemm_select(const ctrl_igemm_desc* d, int group_n, int pinned, char* b
    in ONE launch -- the [M][2048] hidden activation never reaches HBM.  X fp16 [M][ldx] (the LayerNorm output), W1 / b1 the GEGLU-
    interleaved pack of ff.net.0.proj (ctrl_op_pack_linear_w / ctrl_op_pack_vec with geglu = 1: [4096][512], [4096]), W2p the pack of
    ff.net.2 re-ordered along K by ctrl_op_ffn_pack_w2, `out` the descriptor of the OUTPUT GEMM ([M][512]: bias, res / ldres / res_f32,
-   seg[0] row-major, out16 ...; its A / W / K fields are ignored).  ctrl_op_ffn_pack_w2: fp16 [512][2048] linear pack -> fp16 [512][2048]. */
+   seg[0] row-major, out16 ...; its A / W / K fields are ignored).  ctrl_op_ffn_pack_w2: fp16 [512][2048] linear pack -> fp16 [512][2048].
+   Of the output descriptor the kernel honours bias, res / ldres / res_f32, seg[0] (row-major, fp16 or fp32, all 512 columns), out16 / ld16,
+   the AlphaBlender fold (blend_*) and nonfinite; every row stride must be a multiple of 8 elements and every one of those pointers
+   16-byte aligned (the epilogue moves 16-byte pieces); rowvec, act, geglu, res_up = 2, a scale other than 1, scale2_from, out16_lo_off
+   and a bf16 output are refused. */
 typedef struct ctrl_ffn_desc {
     const void* X; int64_t ldx;
     const void* W1; const float* b1;
@@ -157,6 +161,10 @@ typedef struct ctrl_ffn_desc {
     ctrl_igemm_desc out;
 } ctrl_ffn_desc;
 int ctrl_op_ffn(const ctrl_ffn_desc* d, void* stream);
+/* Test ABI.  d[0..n), 1 <= n <= 4, equal M: the feed-forwards of sibling adapter blocks in ONE launch, the way the plans' collector
+   launches them (member g owns workgroups [g * per, g * per + ceil(M / 128)), per = ceil(M / 128) rounded up to a multiple of 8;
+   the rest exit at once); the result of every member is bit for bit what ctrl_op_ffn gives it alone. */
+int ctrl_op_ffn_group(const ctrl_ffn_desc* d, int n, void* stream);
 int ctrl_op_ffn_pack_w2(const void* w2_packed, void* out, int N, int K, void* stream);
 /* Range safety of the fp16 activations (debug aid for real checkpoints: the synthetic N(0, 0.02^2) weights never leave the fp16 range).
    ctrl_range_check(1) -- or CTRL_CHECK_FINITE=1 in the environment -- makes every GEMM / convolution epilogue OR "this fp16 value is
@@ -314,6 +322,14 @@ int ctrl_op_add_rowvec(const void* x, int x_dtype, const float* v, int64_t ldv, 
                        int rows_per_img, int vmod, void* stream);
 int ctrl_op_conv3x3_direct(const void* in, int in_dtype, int in_nchw, const float* w, const float* bias, void* out,
                            int N, int Cin, int Cout, int Hin, int Win, int stride, int silu, void* stream);
+/* Test ABI.  The fp32 stem forms of the direct kernel, which write the residual stream of the backbone UNets (stride 1, pad 1, + bias,
+ * no activation; w fp32 [9][Cin][Cout], out fp32 rows [N*H*W][Cout], Cout % 16 == 0, out 16-byte aligned):
+ *   ctrl_op_conv3x3_direct_f32  in = NCHW [N][Cin][H][W] of in_dtype, Cin = 4 | 8
+ *   ctrl_op_conv3x3_rows_f32    in = fp32 channels-last rows [N*H*W][8] (16-byte aligned), Cin = 8 */
+int ctrl_op_conv3x3_direct_f32(const void* in, int in_dtype, const float* w, const float* bias, void* out, int N, int Cin, int Cout,
+                               int H, int W, void* stream);
+int ctrl_op_conv3x3_rows_f32(const void* in, const float* w, const float* bias, void* out, int N, int Cin, int Cout, int H, int W,
+                             void* stream);
 /* the same 3x3 convolution (pad 1, stride 1|2, + bias, optional SiLU) on the matrix cores for channels-last fp16 input with Cin, Cout in
  * {16, 32}: w fp16 [Cout][9][Cin] (ctrl_op_pack_conv_w with taps = 9) */
 int ctrl_op_conv3x3_small_mfma(const void* x, const void* w, const float* bias, void* out, int N, int Cin, int Cout, int Hin, int Win,

@@ -228,3 +228,40 @@ def assert_attn_close(out, ref, bound, what=""):
                                                             float(ref[first]), float(bound[first]), rows[:8], " ..." if len(rows) > 8 else ""))
     assert rel <= ATTN_REL_INF_TOL, "%s: rel_inf %.3e > %.1e" % (what, rel, ATTN_REL_INF_TOL)
     return worst, rel
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Element-wise check of a fused feed-forward result (tests/test_gpu_ffn_forms.py; self-test: tests/test_ffn_check_host.py)
+#
+#   out = [blend]( ((x W1h^T + b1h) * gelu_erf(x W1g^T + b1g)) W2^T + b2 + res ),  fp16 operands, fp32 accumulation, the hidden activation
+#   rounded to fp16 once, compared with an fp64 reference over the same operands.  The bound follows the kernel's chain
+#       accumulation of the pre-activation (non-zero addends only) -> gelu_erf_f's own derived error -> |gelu'| <= 1.13 and the product ->
+#       one fp32 and one fp16 rounding of P -> the K = 2048 accumulation -> the AlphaBlender fold -> the rounding of the stored value
+#   and is built, term by term, in tests/ffn_forms.py (reference()); nothing in it is measured and there is no slack factor.
+# ---------------------------------------------------------------------------------------------------------------------
+FFN_REL_INF_TOL = 2e-3            # the suite's per-tensor tolerance (tests/test_gpu_ops.py), asserted beside the bound
+
+
+def assert_ffn_close(out, ref, bound, what=""):
+    """every element of `out` finite and within `bound` (ffn_forms.reference) of the fp64 `ref`, AND the per-tensor rel_inf within the
+    suite's tolerance.  Returns (worst |err| / bound, rel_inf)."""
+    o = out.detach().cpu().double()
+    assert o.shape == ref.shape, (what, tuple(o.shape), tuple(ref.shape))
+    assert bool(torch.isfinite(o).all()), "%s: %d non-finite outputs (a poisoned pad reached a kept element); first at %s" % (
+        what, int((~torch.isfinite(o)).sum()), tuple(int(v) for v in (~torch.isfinite(o)).nonzero()[0]))
+    err = (o - ref).abs()
+    worst = float((err / bound).max())
+    rel = float(err.max() / ref.abs().max().clamp_min(1e-12))
+    print("FFN-CHECK %-60s worst err/bound %.3f  rel_inf %.2e" % (what, worst, rel))
+    bad = err > bound
+    if bool(bad.any()):
+        idx = bad.nonzero()
+        first = tuple(int(v) for v in idx[0])
+        rows = sorted({int(v) for v in idx[:, 0]})
+        cols = sorted({int(v) for v in idx[:, 1]})
+        raise AssertionError("%s: %d of %d elements beyond the format-derived bound (worst err/bound %.2f); first at %s: got %.6g want %.6g "
+                             "bound %.3g; rows hit: %s%s; columns hit: %s%s" % (
+                                 what, int(bad.sum()), bad.numel(), worst, first, float(o[first]), float(ref[first]), float(bound[first]),
+                                 rows[:12], " ..." if len(rows) > 12 else "", cols[:12], " ..." if len(cols) > 12 else ""))
+    assert rel <= FFN_REL_INF_TOL, "%s: rel_inf %.3e > %.1e" % (what, rel, FFN_REL_INF_TOL)
+    return worst, rel

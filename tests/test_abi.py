@@ -27,7 +27,10 @@ def test_library_exports_every_declared_symbol():
     assert {"ctrl_op_gn_stats_group", "ctrl_op_gn_apply_group", "ctrl_op_gn_fused_group", "ctrl_gn_launch_shape", "ctrl_op_layernorm_group",
             "ctrl_op_layernorm_add", "ctrl_op_add_rowvec_clip", "ctrl_op_upsample2x_nhwc", "ctrl_op_fill_zero_group",
             "ctrl_op_linear_small_group", "ctrl_op_frameidx_sincos"} <= declared
-    assert lib.ctrl_abi_version() == _lib.ABI_VERSION == 8
+    # the test ABI of the fused feed-forward's grouped launch and of the fp32 stem convolutions (tests/ffn_forms.py,
+    # tests/test_gpu_ffn_forms.py, tests/smallconv_forms.py, tests/test_gpu_smallconv_forms.py)
+    assert {"ctrl_op_ffn_group", "ctrl_op_conv3x3_direct_f32", "ctrl_op_conv3x3_rows_f32"} <= declared
+    assert lib.ctrl_abi_version() == _lib.ABI_VERSION == 9
 
 
 def test_struct_sizes_match_header():
