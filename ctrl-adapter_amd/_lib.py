@@ -184,7 +184,7 @@ class ClipComm(C.Structure):
 
 
 # every symbol include/ctrl_hip.h declares (tests check the library exports all of them)
-ABI_VERSION = 9       # CTRL_ABI_VERSION of include/ctrl_hip.h
+ABI_VERSION = 10      # CTRL_ABI_VERSION of include/ctrl_hip.h
 EXPORTS = [
     "ctrl_abi_version", "ctrl_last_error", "ctrl_prof_begin", "ctrl_prof_end", "ctrl_prof_count", "ctrl_prof_get",
     "ctrl_prof_launch_count", "ctrl_prof_launch_get",
@@ -206,6 +206,7 @@ EXPORTS = [
     "ctrl_text_encoder_create", "ctrl_text_encoder_destroy", "ctrl_text_encoder_forward", "ctrl_text_encoder_id_status",
     "ctrl_op_text_embed", "ctrl_op_text_attn", "ctrl_op_text_final_ln",
     "ctrl_text_encoder_create_ext", "ctrl_text_encoder_forward_ext", "ctrl_text_gemm_ws_bytes", "ctrl_op_text_gemm",
+    "ctrl_op_text_gemm_finish", "ctrl_op_text_proj", "ctrl_op_text_store", "ctrl_op_vision_vt", "ctrl_op_text_final_ln_ext",
     "ctrl_vision_encoder_param_count", "ctrl_vision_encoder_param_spec", "ctrl_vision_encoder_create", "ctrl_vision_encoder_destroy",
     "ctrl_vision_encoder_forward", "ctrl_op_vision_patchify", "ctrl_op_vision_embed", "ctrl_op_vision_cls_ln", "ctrl_op_clip_resize_aa",
     "ctrl_vae_encoder_param_count", "ctrl_vae_encoder_param_spec", "ctrl_vae_encoder_create", "ctrl_vae_encoder_destroy",
@@ -266,6 +267,13 @@ def lib():
         _lib.ctrl_text_gemm_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
         _lib.ctrl_op_text_gemm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                            C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+        _lib.ctrl_op_text_gemm_finish.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+                                                  C.c_int, C.c_int64, C.c_void_p]
+        _lib.ctrl_op_text_proj.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        _lib.ctrl_op_text_store.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]
+        _lib.ctrl_op_vision_vt.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        _lib.ctrl_op_text_final_ln_ext.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
+                                                   C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.ctrl_vision_encoder_destroy.restype = None
         _lib.ctrl_vision_encoder_destroy.argtypes = [C.c_void_p]
         _lib.ctrl_vision_encoder_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -179,4 +179,23 @@ int ctrl_op_text_gemm(const void* x, const void* W, const float* bias, int M, in
     return op_text_gemm((const half_t*)x, (const half_t*)W, bias, M, N, K, act, res, y, y_dtype, (float*)ws, (size_t)ws_bytes, S(stream));
 }
 
+int ctrl_op_text_gemm_finish(const float* ws, int splits, int M, int N, const float* bias, int act, const float* res, int64_t ldres, void* y,
+                             int y_dtype, int64_t ldy, void* stream) {
+    return op_text_gemm_finish(ws, splits, M, N, bias, act, res, (long)ldres, y, y_dtype, (long)ldy, S(stream));
+}
+
+int ctrl_op_text_proj(const float* pooled32, const float* Wp, int N, int C, int P, void* out, int out_dtype, void* stream) {
+    return op_text_proj(pooled32, Wp, N, C, P, out, out_dtype, S(stream));
+}
+
+int ctrl_op_text_store(const float* x, void* y, int y_dtype, int64_t n, void* stream) {
+    CTRL_CHECK(n >= 0, "text_store: n must be >= 0");
+    return op_text_store(x, y, y_dtype, (size_t)n, S(stream));
+}
+
+int ctrl_op_text_final_ln_ext(const void* x, int x_dtype, int rows, int C, const float* gamma, const float* beta, float eps,
+                              void* y, int y_dtype, const int64_t* ids, int L, int eos_token_id, void* pooled, float* pooled32, void* stream) {
+    return op_text_final_ext(x, x_dtype, rows, C, gamma, beta, eps, y, y_dtype, ids, L, eos_token_id, pooled, pooled32, S(stream));
+}
+
 }  // extern "C"

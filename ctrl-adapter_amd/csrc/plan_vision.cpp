@@ -185,4 +185,8 @@ int ctrl_op_clip_resize_aa(const void* src, int src_dtype, int N, int H, int W, 
     return op_clip_resize_aa(src, src_dtype, N, H, W, OH, OW, mean_std, out, out_dtype, S(stream));
 }
 
+int ctrl_op_vision_vt(const void* v, int64_t ld, void* vt, int N, int L, int C, int Lkpad, void* stream) {
+    return op_vision_vt((const half_t*)v, (long)ld, (half_t*)vt, N, L, C, Lkpad, S(stream));
+}
+
 }  // extern "C"

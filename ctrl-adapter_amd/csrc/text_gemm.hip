@@ -162,6 +162,9 @@ int op_text_gemm(const half_t* x, const half_t* W, const float* bias, int M, int
     CTRL_CHECK((long)M * N <= (1L << 30) && (long)M * K <= (1L << 30) && (long)N * K <= (1L << 30), "text_gemm: problem too large");
     CTRL_CHECK((((uintptr_t)x | (uintptr_t)W) & 15) == 0 && ((uintptr_t)ws & 15) == 0, "text_gemm: x, W and ws must be 16-byte aligned");
     CTRL_CHECK((!bias || ((uintptr_t)bias & 15) == 0) && (!res || ((uintptr_t)res & 15) == 0), "text_gemm: bias / res must be 16-byte aligned");
+    // (the finish launch checks these as well: refused here, nothing has been launched yet)
+    CTRL_CHECK(act == 0 || act == 2 || act == 3, "text_gemm: act must be 0, 2 or 3");
+    CTRL_CHECK(y_dt >= DT_F32 && y_dt <= DT_BF16, "text_gemm: bad output dtype");
     const int splits = text_gemm_splits(N, K);
     CTRL_CHECK(ws_bytes >= text_gemm_ws_bytes(M, N, K), "text_gemm: workspace too small");
     const int ntn = (N + kTgBN - 1) / kTgBN;

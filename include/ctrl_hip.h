@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define CTRL_ABI_VERSION 9
+#define CTRL_ABI_VERSION 10
 
 /* element types of boundary tensors */
 enum { CTRL_F32 = 0, CTRL_F16 = 1, CTRL_BF16 = 2 };
@@ -624,6 +624,18 @@ int ctrl_text_encoder_forward_ext(ctrl_text_encoder* h, const int64_t* input_ids
 int64_t ctrl_text_gemm_ws_bytes(int M, int N, int K);
 int ctrl_op_text_gemm(const void* x, const void* W, const float* bias, int M, int N, int K, int act, const float* res, void* y,
                       int y_dtype, void* ws, int64_t ws_bytes, void* stream);
+/* test ABI of the two towers' remaining kernels (tests/tower_forms.py, tests/test_gpu_tower_forms.py): what a plan alone reaches.
+ * text_gemm_finish: y [M][ldy] (y_dtype) = act(sum over ws [splits][M][N] fp32 in split order + bias) (+ res fp32 [M][ldres]); N % 4 == 0.
+ * text_proj: out [N][P] (out_dtype) = pooled32 [N][C] . Wp [P][C]^T, fp32.  text_store: y [n] (y_dtype) = x [n] fp32.
+ * vision_vt: vt fp16 [N][C][Lkpad] = v fp16 [N*L][ld] transposed per image, columns L..Lkpad-1 zero; C % 32 == 0, Lkpad % 32 == 0.
+ * text_final_ln_ext: ctrl_op_text_final_ln plus pooled32 [rows / L][C], the pooled row in fp32 (either pooled may be NULL). */
+int ctrl_op_text_gemm_finish(const float* ws, int splits, int M, int N, const float* bias, int act, const float* res, int64_t ldres, void* y,
+                             int y_dtype, int64_t ldy, void* stream);
+int ctrl_op_text_proj(const float* pooled32, const float* Wp, int N, int C, int P, void* out, int out_dtype, void* stream);
+int ctrl_op_text_store(const float* x, void* y, int y_dtype, int64_t n, void* stream);
+int ctrl_op_vision_vt(const void* v, int64_t ld, void* vt, int N, int L, int C, int Lkpad, void* stream);
+int ctrl_op_text_final_ln_ext(const void* x, int x_dtype, int rows, int C, const float* gamma, const float* beta, float eps,
+                              void* y, int y_dtype, const int64_t* ids, int L, int eos_token_id, void* pooled, float* pooled32, void* stream);
 
 /* ---- CLIP vision tower (transformers CLIPVisionModelWithProjection: the image_encoder of SVD and I2VGen-XL, CLIP ViT-H/14;
  * svd/pipelines/svd_controlnet_adapter_pipeline.py:166-212, i2vgen_xl/pipelines/i2vgen_xl_controlnet_adapter_pipeline.py:366-396) ----

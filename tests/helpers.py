@@ -180,13 +180,19 @@ class Guarded:
 ATTN_REL_INF_TOL = 2e-3           # the suite's per-tensor tolerance (tests/test_gpu_ops.py), asserted beside the bound
 
 
-def attn_reference(q, k, v, c, D=None, p_fp16=True):
+def attn_reference(q, k, v, c, D=None, p_fp16=True, mask=None):
     """fp64 reference and element-wise bound of softmax_2(c * q k^T) v.  q [N][Lq][D], k, v [N][Lk][D] (N = batch * heads; k, v may
-    have N = 1: broadcast), c: float.  Returns (ref, bound), both [N][Lq][D] fp64."""
+    have N = 1: broadcast), c: float.  mask (bool [Lq][Lk] or [N][Lq][Lk], True = visible; every query sees at least one key): a masked
+    weight is exactly 0 and carries no error term, and the largest |q| . |k| is taken over the visible keys.
+    Returns (ref, bound), both [N][Lq][D] fp64."""
     q, k, v = q.double(), k.double(), v.double()
     D = D or q.shape[-1]
     Lk = k.shape[-2]
     s = (q @ k.transpose(-1, -2)) * c
+    A = (q.abs() @ k.abs().transpose(-1, -2)) * abs(c)
+    if mask is not None:
+        s = s.masked_fill(~mask, float("-inf"))
+        A = A.masked_fill(~mask, 0.0)
     smax = s.max(-1, keepdim=True).values
     e = torch.exp2(s - smax)
     l = e.sum(-1, keepdim=True)
@@ -194,13 +200,15 @@ def attn_reference(q, k, v, c, D=None, p_fp16=True):
     va = v.abs()
     ref = w @ v
     mag = w @ va
-    A = (q.abs() @ k.abs().transpose(-1, -2)) * abs(c)
     delta = (D + 8) * 2.0 ** -24 * (A + A.max(-1, keepdim=True).values)
     wg = w * (torch.exp2(delta) - 1 + 2.0 ** -22)
     sg = wg.sum(-1, keepdim=True)
     bound = (wg @ va + ref.abs() * sg) / (1 - sg)
     if p_fp16:
-        bound = bound + torch.maximum(2.0 ** -11 * w, 2.0 ** -25 / l) @ va
+        pr = torch.maximum(2.0 ** -11 * w, 2.0 ** -25 / l)
+        if mask is not None:
+            pr = pr.masked_fill(~mask, 0.0)
+        bound = bound + pr @ va
     bound = bound + 2 * (Lk + (Lk + 63) // 64 + 8) * 2.0 ** -24 * mag
     bound = bound + 2.0 ** -11 * ref.abs() + 2.0 ** -25
     return ref, bound

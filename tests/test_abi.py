@@ -30,7 +30,9 @@ def test_library_exports_every_declared_symbol():
     # the test ABI of the fused feed-forward's grouped launch and of the fp32 stem convolutions (tests/ffn_forms.py,
     # tests/test_gpu_ffn_forms.py, tests/smallconv_forms.py, tests/test_gpu_smallconv_forms.py)
     assert {"ctrl_op_ffn_group", "ctrl_op_conv3x3_direct_f32", "ctrl_op_conv3x3_rows_f32"} <= declared
-    assert lib.ctrl_abi_version() == _lib.ABI_VERSION == 9
+    # the test ABI of the CLIP towers' kernels that only a plan reached (tests/tower_forms.py, tests/test_gpu_tower_forms.py)
+    assert {"ctrl_op_text_gemm_finish", "ctrl_op_text_proj", "ctrl_op_text_store", "ctrl_op_vision_vt", "ctrl_op_text_final_ln_ext"} <= declared
+    assert lib.ctrl_abi_version() == _lib.ABI_VERSION == 10
 
 
 def test_struct_sizes_match_header():
