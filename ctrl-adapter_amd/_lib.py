@@ -225,6 +225,8 @@ EXPORTS = [
     "ctrl_sampler_create", "ctrl_sampler_destroy", "ctrl_sampler_reset", "ctrl_sampler_scalars", "ctrl_sampler_model_input",
     "ctrl_sampler_step", "ctrl_op_sampler_reset", "ctrl_op_sampler_model_input", "ctrl_op_sampler_step", "ctrl_op_sampler_launch_shape",
     "ctrl_op_merge_gather_group", "ctrl_op_merge_gather_launch_shape",
+    "ctrl_op_pack_conv_w_ovf", "ctrl_op_pack_conv_w_dup_ovf", "ctrl_op_pack_conv_w_phase_ovf", "ctrl_op_pack_linear_w_ovf",
+    "ctrl_op_nhwc_to_nchw_map", "ctrl_op_unet_conv_out", "ctrl_op_i2v_frames", "ctrl_op_vae_conv_in",
 ]
 
 _lib = None
@@ -355,6 +357,15 @@ def lib():
                C.c_int, C.c_int]
         _lib.ctrl_op_merge_gather_group.argtypes = _mg + [C.c_void_p]
         _lib.ctrl_op_merge_gather_launch_shape.argtypes = _mg + [C.POINTER(C.c_int)] * 3
+        _lib.ctrl_op_pack_conv_w_ovf.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.ctrl_op_pack_conv_w_dup_ovf.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.ctrl_op_pack_conv_w_phase_ovf.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.ctrl_op_pack_linear_w_ovf.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.ctrl_op_nhwc_to_nchw_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
+        _lib.ctrl_op_unet_conv_out.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                               C.c_int, C.c_int, C.c_int, C.c_void_p]
+        _lib.ctrl_op_i2v_frames.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        _lib.ctrl_op_vae_conv_in.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         _lib.ctrl_rccl_comm_destroy.restype = None
         _lib.ctrl_rccl_comm_destroy.argtypes = [C.c_void_p]
         _lib.ctrl_rccl_comm_bytes_sent.restype = C.c_int64

@@ -213,6 +213,33 @@ int ctrl_op_pack_linear_w(const void* w, int dtype, void* out, int N, int K, int
 int ctrl_op_pack_vec(const void* v, int dtype, float* out, int N, int geglu, void* stream) {
     return op_pack_vec(v, dtype, out, N, geglu, S(stream));
 }
+// test ABI of the helper kernels (tests/helper_forms.py): the packers with the caller's fp16 range flag, the transpose with an image map,
+// and the three per-pixel kernels only a plan reached
+int ctrl_op_pack_conv_w_ovf(const void* w, int dtype, void* out, int Cout, int Cin, int taps, int32_t* ovf, void* stream) {
+    return op_pack_conv_w(w, dtype, H(out), Cout, Cin, taps, S(stream), ovf);
+}
+int ctrl_op_pack_conv_w_dup_ovf(const void* w, int dtype, void* out, int Cout, int Cin, int taps, int32_t* ovf, void* stream) {
+    return op_pack_conv_w_dup(w, dtype, H(out), Cout, Cin, taps, S(stream), ovf);
+}
+int ctrl_op_pack_conv_w_phase_ovf(const void* w, int dtype, void* out, int Cout, int Cin, int32_t* ovf, void* stream) {
+    return op_pack_conv_w_phase(w, dtype, H(out), Cout, Cin, S(stream), ovf);
+}
+int ctrl_op_pack_linear_w_ovf(const void* w, int dtype, void* out, int N, int K, int geglu, int32_t* ovf, void* stream) {
+    return op_pack_linear_w(w, dtype, H(out), N, K, geglu, S(stream), ovf);
+}
+int ctrl_op_nhwc_to_nchw_map(const void* x, void* y, int dtype, int N, int C, int HW, float scale, const int32_t* img_map, void* stream) {
+    return op_nhwc_to_nchw(CH(x), y, dtype, N, C, HW, scale, S(stream), img_map);
+}
+int ctrl_op_unet_conv_out(const void* x, const float* w, const float* bias, void* out, int out_dtype, int N, int H, int W, int C, int Cout,
+                          int layout, int frames, void* stream) {
+    return op_unet_conv_out(CH(x), w, bias, out, out_dtype, N, H, W, C, Cout, S(stream), layout, frames);
+}
+int ctrl_op_i2v_frames(const void* x, int dtype, float* y, int B, int F, int HW, void* stream) {
+    return op_i2v_frames(x, dtype, y, B, F, HW, S(stream));
+}
+int ctrl_op_vae_conv_in(const void* px, int dtype, const float* w, const float* b, float* out, int H, int W, int Cout, void* stream) {
+    return op_vae_conv_in(px, dtype, w, b, out, H, W, Cout, S(stream));
+}
 int ctrl_router_weights(const float* wg, const int* mask_host, float* weights_out, int R, int E, int equal_weights, void* stream) {
     return op_router_softmax(wg, mask_host, weights_out, R, E, equal_weights, S(stream));
 }

@@ -65,7 +65,10 @@ void prof_symbol(const char* fmt, ...);       // kernel symbol with its template
 __device__ __forceinline__ float bf16_to_f32(u16 v) { return __uint_as_float(((unsigned)v) << 16); }
 __device__ __forceinline__ u16 f32_to_bf16(float f) {
     unsigned u = __float_as_uint(f);
-    unsigned r = u + 0x7FFFu + ((u >> 16) & 1u);   // RNE (NaN not expected on this path)
+    // RNE.  A NaN is rounded as a number: the canonical one (0x7FC00000, what the hardware produces), a widened bf16 NaN and +-inf
+    // survive; a NaN whose upper seven mantissa bits are all ones and whose lower sixteen round up (0x7FFF8000 and above) carries out of
+    // the exponent and becomes +-0 (tests/test_gpu_helper_forms.py)
+    unsigned r = u + 0x7FFFu + ((u >> 16) & 1u);
     return (u16)(r >> 16);
 }
 __device__ __forceinline__ float load_as_f32(const void* p, size_t i, int dt) {

@@ -721,6 +721,17 @@ int op_merge_gather_group(const MergeSlot* slots, int n_slots, const float* w, i
     else LAUNCH("merge_gather", merge_gather_kernel<1>, dim3(blocks), dim3(256), 0, s, a);
     return 0;
 }
+namespace {
+// what every packer entry refuses before its launch: a null tensor, a dtype the loads do not know, an empty or negative extent, and
+// 2^31 or more elements (pack_vec indexes with int, the others split rows and columns into int; no weight of a supported model comes near)
+int pack_args(const void* src, const void* dst, int dtype, const char* who, double elems, bool positive) {
+    CTRL_CHECK(src && dst, std::string(who) + ": null pointer");
+    CTRL_CHECK(dtype >= DT_F32 && dtype <= DT_BF16, std::string(who) + ": the source must be fp32, fp16 or bf16");
+    CTRL_CHECK(positive, std::string(who) + ": every extent must be at least 1");
+    CTRL_CHECK(elems < 2147483648.0, std::string(who) + ": too many elements");
+    return 0;
+}
+}  // namespace
 int op_router_softmax(const float* wg, const int* mask, float* out, int R, int E, int equal_weights, hipStream_t s) {
     CTRL_CHECK(E >= 1 && E <= 16, "router: 1..16 experts supported");
     RouterMask rm;
@@ -729,27 +740,34 @@ int op_router_softmax(const float* wg, const int* mask, float* out, int R, int E
     return 0;
 }
 int op_pack_conv_w(const void* w, int dtype, half_t* out, int Cout, int Cin, int taps, hipStream_t s, int* ovf) {
+    TRY(pack_args(w, out, dtype, "pack_conv_w", (double)Cout * Cin * taps, Cout >= 1 && Cin >= 1 && taps >= 1));
     LAUNCH("pack", pack_conv_w_kernel, dim3(grid_for((size_t)Cout * Cin * taps)), dim3(256), 0, s, w, dtype, out, Cout, Cin, taps, ovf);
     return 0;
 }
 int op_pack_conv_w_dup(const void* w, int dtype, half_t* out, int Cout, int Cin, int taps, hipStream_t s, int* ovf) {
+    TRY(pack_args(w, out, dtype, "pack_conv_w_dup", 2.0 * Cout * Cin * taps, Cout >= 1 && Cin >= 1 && taps >= 1));
     LAUNCH("pack", pack_conv_w_dup_kernel, dim3(grid_for((size_t)Cout * Cin * taps * 2)), dim3(256), 0, s, w, dtype, out, Cout, Cin, taps, ovf);
     return 0;
 }
 int op_pack_conv_w_phase(const void* w, int dtype, half_t* out, int Cout, int Cin, hipStream_t s, int* ovf) {
+    TRY(pack_args(w, out, dtype, "pack_conv_w_phase", 16.0 * Cout * Cin, Cout >= 1 && Cin >= 1));
     LAUNCH("pack", pack_conv_w_phase_kernel, dim3(grid_for((size_t)Cout * Cin * 16)), dim3(256), 0, s, w, dtype, out, Cout, Cin, ovf);
     return 0;
 }
 int op_pack_conv_w_direct(const void* w, int dtype, float* out, int Cout, int Cin, hipStream_t s) {
+    TRY(pack_args(w, out, dtype, "pack_conv_w_direct", 9.0 * Cout * Cin, Cout >= 1 && Cin >= 1));
     LAUNCH("pack", pack_conv_w_direct_kernel, dim3(grid_for((size_t)Cout * Cin * 9)), dim3(256), 0, s, w, dtype, out, Cout, Cin);
     return 0;
 }
 int op_pack_linear_w(const void* w, int dtype, half_t* out, int N, int K, int geglu, hipStream_t s, int* ovf) {
+    TRY(pack_args(w, out, dtype, "pack_linear_w", (double)N * K, N >= 1 && K >= 1));
     CTRL_CHECK(!geglu || N % 32 == 0, "pack_linear_w: GEGLU needs N % 32 == 0");
     LAUNCH("pack", pack_linear_w_kernel, dim3(grid_for((size_t)N * K)), dim3(256), 0, s, w, dtype, out, N, K, geglu, ovf);
     return 0;
 }
 int op_pack_vec(const void* v, int dtype, float* out, int N, int geglu, hipStream_t s) {
+    TRY(pack_args(v, out, dtype, "pack_vec", (double)N, N >= 1));
+    CTRL_CHECK(!geglu || N % 32 == 0, "pack_vec: GEGLU needs N % 32 == 0");
     LAUNCH("pack", pack_vec_kernel, dim3((N + 255) / 256), dim3(256), 0, s, v, dtype, out, N, geglu);
     return 0;
 }

@@ -17,30 +17,39 @@ def _f16(*shape, device="cuda"):
     return torch.empty(*shape, dtype=torch.float16, device=device)
 
 
-def pack_conv_w(w):
+def pack_conv_w(w, ovf=None):
     """[Cout][Cin][kh][kw] -> fp16 [Cout][kh*kw][Cin]"""
     cout, cin = w.shape[0], w.shape[1]
     taps = w[0, 0].numel()
     out = _f16(cout, taps * cin)
+    if ovf is not None:          # the plans' fp16 range flag (device int32): set to 1, never cleared
+        L.check(L.lib().ctrl_op_pack_conv_w_ovf(L.ptr(w.contiguous()), L.dtype_code(w.dtype), L.ptr(out), cout, cin, taps, L.ptr(ovf), L.cur_stream()))
+        return out
     L.check(L.lib().ctrl_op_pack_conv_w(L.ptr(w.contiguous()), L.dtype_code(w.dtype), L.ptr(out), cout, cin, taps, L.cur_stream()))
     return out
 
 
-def pack_conv_w_dup(w):
+def pack_conv_w_dup(w, ovf=None):
     """[Cout][Cin][kh][kw] -> fp16 [Cout][kh*kw][2*Cin] (split-operand convolution: every tap's weights twice)"""
     cout, cin = w.shape[0], w.shape[1]
     taps = w[0, 0].numel()
     out = _f16(cout, taps * 2 * cin)
+    if ovf is not None:          # the plans' fp16 range flag (device int32): set to 1, never cleared
+        L.check(L.lib().ctrl_op_pack_conv_w_dup_ovf(L.ptr(w.contiguous()), L.dtype_code(w.dtype), L.ptr(out), cout, cin, taps, L.ptr(ovf), L.cur_stream()))
+        return out
     L.check(L.lib().ctrl_op_pack_conv_w_dup(L.ptr(w.contiguous()), L.dtype_code(w.dtype), L.ptr(out), cout, cin, taps, L.cur_stream()))
     return out
 
 
-def pack_conv_w_phase(w):
+def pack_conv_w_phase(w, ovf=None):
     """[Cout][Cin][3][3] -> fp16 [4][Cout][4*Cin]: the four 2x2 phase convs of a 3x3 conv over a nearest x2 up-sampled map
     (include/ctrl_hip.h: ctrl_op_pack_conv_w_phase; the W operand of an IG_CONV2D_PHASE problem)"""
     cout, cin = w.shape[0], w.shape[1]
     assert tuple(w.shape[2:]) == (3, 3)
     out = _f16(4, cout, 4 * cin, device=w.device)
+    if ovf is not None:          # the plans' fp16 range flag (device int32): set to 1, never cleared
+        L.check(L.lib().ctrl_op_pack_conv_w_phase_ovf(L.ptr(w.contiguous()), L.dtype_code(w.dtype), L.ptr(out), cout, cin, L.ptr(ovf), L.cur_stream()))
+        return out
     L.check(L.lib().ctrl_op_pack_conv_w_phase(L.ptr(w.contiguous()), L.dtype_code(w.dtype), L.ptr(out), cout, cin, L.cur_stream()))
     return out
 
@@ -52,9 +61,13 @@ def pack_conv_w_direct(w):
     return out
 
 
-def pack_linear_w(w, geglu=False):
+def pack_linear_w(w, geglu=False, ovf=None):
     n, k = w.shape
     out = _f16(n, k)
+    if ovf is not None:
+        L.check(L.lib().ctrl_op_pack_linear_w_ovf(L.ptr(w.contiguous()), L.dtype_code(w.dtype), L.ptr(out), n, k, int(geglu), L.ptr(ovf),
+                                                  L.cur_stream()))
+        return out
     L.check(L.lib().ctrl_op_pack_linear_w(L.ptr(w.contiguous()), L.dtype_code(w.dtype), L.ptr(out), n, k, int(geglu), L.cur_stream()))
     return out
 
@@ -518,6 +531,49 @@ def add_rowvec(x, v, rows_per_img, vmod):
     L.check(L.lib().ctrl_op_add_rowvec(L.ptr(x), L.dtype_code(x.dtype), L.ptr(v), C.c_int64(v.shape[-1]), L.ptr(y), L.dtype_code(y.dtype),
                                        C.c_size_t(M), Cc, rows_per_img, vmod, L.cur_stream()))
     return y
+
+
+def blend_into(xs, xt, mix, y, n=None):
+    """y = sigmoid(mix) xs + (1 - sigmoid(mix)) xt over the first n elements (default: all of xs); xs, xt, y fp16 or fp32, each its own"""
+    L.check(L.lib().ctrl_op_blend(L.ptr(xs), L.dtype_code(xs.dtype), L.ptr(xt), L.dtype_code(xt.dtype), L.ptr(mix), L.ptr(y),
+                                  L.dtype_code(y.dtype), C.c_size_t(xs.numel() if n is None else n), L.cur_stream()))
+
+
+def add_rowvec_into(x, v, ldv, y, M, Cc, rows_per_img, vmod):
+    """y[m] = x[m] + v[(m // rows_per_img) % vmod] over M dense rows of Cc; v rows ldv apart; y may be x, and of another dtype"""
+    L.check(L.lib().ctrl_op_add_rowvec(L.ptr(x), L.dtype_code(x.dtype), L.ptr(v), C.c_int64(ldv), L.ptr(y), L.dtype_code(y.dtype),
+                                       C.c_size_t(M), Cc, rows_per_img, vmod, L.cur_stream()))
+
+
+def nhwc_to_nchw_into(x, y, N, Cc, HW, scale=1.0, img_map=None):
+    """fp16 [N][HW][Cc] -> y [..][Cc][HW] * scale in y's dtype; img_map (int32 device [N]): source image n lands at image img_map[n]"""
+    L.check(L.lib().ctrl_op_nhwc_to_nchw_map(L.ptr(x), L.ptr(y), L.dtype_code(y.dtype), N, Cc, HW, C.c_float(scale), L.ptr(img_map),
+                                             L.cur_stream()))
+
+
+CONV_OUT_NCHW, CONV_OUT_NCFHW, CONV_OUT_ROWS = 0, 1, 2
+
+
+def unet_conv_out(x, w_direct, bias, out, N, H, W, Cc, Cout, layout=CONV_OUT_NCHW, frames=1):
+    """the backbone UNets' conv_out: x fp16 [N][H][W][Cc], w_direct = pack_conv_w_direct(w) -> out in its dtype and `layout`"""
+    L.check(L.lib().ctrl_op_unet_conv_out(L.ptr(x), L.ptr(w_direct), L.ptr(bias), L.ptr(out), L.dtype_code(out.dtype), N, H, W, Cc, Cout,
+                                          layout, frames, L.cur_stream()))
+
+
+def i2v_frames(x, y, B, F, HW):
+    """[B][4][F][HW] of any dtype -> fp32 [(b f)][4][HW]"""
+    L.check(L.lib().ctrl_op_i2v_frames(L.ptr(x), L.dtype_code(x.dtype), L.ptr(y), B, F, HW, L.cur_stream()))
+
+
+def vae_conv_in(px, w_direct, bias, out, H, W, Cout):
+    """the KL-VAE encoder's conv_in of one image: NCHW pixels [3][H][W] -> fp32 rows [H*W][Cout]"""
+    L.check(L.lib().ctrl_op_vae_conv_in(L.ptr(px), L.dtype_code(px.dtype), L.ptr(w_direct), L.ptr(bias), L.ptr(out), H, W, Cout,
+                                        L.cur_stream()))
+
+
+def vae_row_softmax(S, lds, P, ldp, rows, Lr, Lpad):
+    """P[r][:Lr] = softmax(S[r][:Lr]) in fp16, P[r][Lr:Lpad] = 0; rows lds / ldp apart"""
+    L.check(L.lib().ctrl_op_vae_row_softmax(L.ptr(S), lds, L.ptr(P), ldp, rows, Lr, Lpad, L.cur_stream()))
 
 
 def conv3x3_direct(x, w_direct, bias, Cout, stride=1, silu=False, nchw=False, out=None):

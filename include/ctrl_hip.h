@@ -353,6 +353,24 @@ int ctrl_op_pack_conv_w_direct(const void* w, int dtype, float* out, int Cout, i
 int ctrl_op_pack_conv_w_phase(const void* w, int dtype, void* out, int Cout, int Cin, void* stream);
 int ctrl_op_pack_linear_w(const void* w, int dtype, void* out, int N, int K, int geglu, void* stream);
 int ctrl_op_pack_vec(const void* v, int dtype, float* out, int N, int geglu, void* stream);
+/* Test ABI of the helper kernels (tests/helper_forms.py, tests/test_gpu_helper_forms.py).
+   The GEMM-weight packers with the fp16 range flag the plans pass: ovf (device int32, may be NULL) is set to 1 when a value to store --
+   judged in fp32, before the rounding -- lies outside [-65504, 65504] or is inf / nan; it is never cleared.
+   nhwc_to_nchw_map: ctrl_op_nhwc_to_nchw with img_map (device int32 [N], may be NULL): source image n is written as image img_map[n].
+   unet_conv_out: 3x3, pad 1, x fp16 channels-last [N][H][W][C] (16-byte aligned, C a multiple of 8 from 16), w fp32 [9][C][Cout]
+   (ctrl_op_pack_conv_w_direct), Cout <= 4, + bias -> out in out_dtype; layout 0: [N][Cout][H][W], 1: [N / frames][Cout][frames][H][W]
+   (image n = (b, f)), 2: channels-last rows [N*H*W][Cout].
+   i2v_frames: [B][4][F][HW] of dtype -> fp32 [(b f)][4][HW].
+   vae_conv_in: one image, NCHW pixels [3][H][W] of dtype, w fp32 [9][3][Cout], Cout % 16 == 0 -> fp32 rows [H*W][Cout] (16-byte aligned) */
+int ctrl_op_pack_conv_w_ovf(const void* w, int dtype, void* out, int Cout, int Cin, int taps, int32_t* ovf, void* stream);
+int ctrl_op_pack_conv_w_dup_ovf(const void* w, int dtype, void* out, int Cout, int Cin, int taps, int32_t* ovf, void* stream);
+int ctrl_op_pack_conv_w_phase_ovf(const void* w, int dtype, void* out, int Cout, int Cin, int32_t* ovf, void* stream);
+int ctrl_op_pack_linear_w_ovf(const void* w, int dtype, void* out, int N, int K, int geglu, int32_t* ovf, void* stream);
+int ctrl_op_nhwc_to_nchw_map(const void* x, void* y, int dtype, int N, int C, int HW, float scale, const int32_t* img_map, void* stream);
+int ctrl_op_unet_conv_out(const void* x, const float* w, const float* bias, void* out, int out_dtype, int N, int H, int W, int C, int Cout,
+                          int layout, int frames, void* stream);
+int ctrl_op_i2v_frames(const void* x, int dtype, float* y, int B, int F, int HW, void* stream);
+int ctrl_op_vae_conv_in(const void* px, int dtype, const float* w, const float* b, float* out, int H, int W, int Cout, void* stream);
 
 /* ---------------------------------------------------------------- plan level */
 /* A named view of one state-dict tensor (reference layout, device memory). */

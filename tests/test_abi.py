@@ -32,6 +32,10 @@ def test_library_exports_every_declared_symbol():
     assert {"ctrl_op_ffn_group", "ctrl_op_conv3x3_direct_f32", "ctrl_op_conv3x3_rows_f32"} <= declared
     # the test ABI of the CLIP towers' kernels that only a plan reached (tests/tower_forms.py, tests/test_gpu_tower_forms.py)
     assert {"ctrl_op_text_gemm_finish", "ctrl_op_text_proj", "ctrl_op_text_store", "ctrl_op_vision_vt", "ctrl_op_text_final_ln_ext"} <= declared
+    # the test ABI of the helper kernels: the packers with the caller's fp16 range flag, the transpose with an image map and the three
+    # per-pixel kernels only a plan reached (tests/helper_forms.py, tests/test_gpu_helper_forms.py)
+    assert {"ctrl_op_pack_conv_w_ovf", "ctrl_op_pack_conv_w_dup_ovf", "ctrl_op_pack_conv_w_phase_ovf", "ctrl_op_pack_linear_w_ovf",
+            "ctrl_op_nhwc_to_nchw_map", "ctrl_op_unet_conv_out", "ctrl_op_i2v_frames", "ctrl_op_vae_conv_in"} <= declared
     assert lib.ctrl_abi_version() == _lib.ABI_VERSION == 10
 
 
