@@ -275,4 +275,28 @@ int ctrl_prepare_images(const void* src_u8, int F, int Hin, int Win, const int32
     return op_prepare_images((const unsigned char*)src_u8, F, Hin, Win, hbounds, hk, hks, vbounds, vk, vks, (unsigned char*)tmp_u8,
                              out, out_dtype, W, H, repeat, cfg, S(stream));
 }
+int ctrl_op_canny_map(const void* src_u8, int N, int H, int W, int C, double low, double high, void* map, void* stream) {
+    return op_canny_map((const unsigned char*)src_u8, N, H, W, C, low, high, (unsigned char*)map, S(stream));
+}
+int ctrl_op_canny_hysteresis(void* map, int N, int H, int W, void* ws, int64_t ws_bytes, int* passes, int* readbacks, void* stream) {
+    return op_canny_hysteresis((unsigned char*)map, N, H, W, ws, (long)ws_bytes, passes, readbacks, S(stream));
+}
+int ctrl_op_canny_finish(const void* map, int N, int H, int W, int out_channels, void* out, void* stream) {
+    return op_canny_finish((const unsigned char*)map, N, H, W, out_channels, (unsigned char*)out, S(stream));
+}
+int ctrl_canny(const void* src_u8, int N, int H, int W, int C, double low, double high, int out_channels, void* out, void* ws,
+               int64_t ws_bytes, int* passes, int* readbacks, void* stream) {
+    return op_canny((const unsigned char*)src_u8, N, H, W, C, low, high, out_channels, (unsigned char*)out, ws, (long)ws_bytes, passes,
+                    readbacks, S(stream));
+}
+int64_t ctrl_canny_ws_bytes(int N, int H, int W) {
+    if (N < 1 || H < 1 || W < 1 || (double)N * H * W * 3 > 2147483647.0) return 0;      // what every entry above refuses
+    return (int64_t)canny_ws_bytes(N, H, W);
+}
+int ctrl_canny_launch_shape(int H, int W, int* tile_h, int* tile_w) {
+    CTRL_CHECK(tile_h && tile_w, "canny_launch_shape: null pointer");
+    CTRL_CHECK(H >= 1 && W >= 1, "canny_launch_shape: H and W must be at least 1");
+    canny_launch_shape(tile_h, tile_w);
+    return 0;
+}
 }

@@ -352,6 +352,21 @@ int op_prepare_images(const unsigned char* src, int F, int Hin, int Win, const i
                       const int* vbounds, const int* vk, int vks, unsigned char* tmp, void* out, int out_dtype,
                       int W, int H, int rep, int cfg, hipStream_t s);
 
+// ------------------------------------------------------------------------------------------
+// Canny condition extraction (model/ctrl_helper.py:171-179), cv2.Canny(img, low, high) bit for bit (canny.hip):
+//   src uint8 [N][H][W][C], C = 1 | 3 -> map uint8 [N][H][W] (0 none, 1 weak, 2 strong) -> hysteresis in place, pass by pass until a
+//   pass promotes nothing (reads a flag back: not capturable) -> out uint8 [N][H][W] | [N][H][W][3] of 0 / 255.
+//   ws: canny_ws_bytes(N, H, W) for op_canny (flag block + map); op_canny_hysteresis alone needs the 256-byte flag block.
+//   *passes = passes up to and including the first that promoted nothing, *readbacks = flag readbacks (host synchronisations).
+// ------------------------------------------------------------------------------------------
+void canny_launch_shape(int* tile_h, int* tile_w);
+long canny_ws_bytes(int N, int H, int W);
+int op_canny_map(const unsigned char* src, int N, int H, int W, int C, double low, double high, unsigned char* map, hipStream_t s);
+int op_canny_hysteresis(unsigned char* map, int N, int H, int W, void* ws, long ws_bytes, int* passes, int* readbacks, hipStream_t s);
+int op_canny_finish(const unsigned char* map, int N, int H, int W, int out_channels, unsigned char* out, hipStream_t s);
+int op_canny(const unsigned char* src, int N, int H, int W, int C, double low, double high, int out_channels, unsigned char* out,
+             void* ws, long ws_bytes, int* passes, int* readbacks, hipStream_t s);
+
 
 // ------------------------------------------------------------------------------------------
 // Grouped launches over sibling problems (round 5).  The adapter blocks of one pyramid level are independent and have identical

@@ -34,6 +34,7 @@ enum PolicyKey {
     P_CN_BATCH_LANES,          // CTRL_CN_BATCH_LANES=1: ControlNetModel.forward splits a batch >= 8 over two stream lanes (Python mirror; measured: no gain)
     P_CONV_UP_PHASE,           // CTRL_CONV_UP_PHASE=0: conv1 of an up-sampling ResNet keeps the 9-tap gather over the x2 map (default: four 2x2 phase convs)
     P_UNET_SPLIT,              // CTRL_UNET_SPLIT=1: split [hi | lo] operands for the backbone UNets' (SVD, SDXL) ResNet convolutions (default: plain fp16 operands)
+    P_CANNY_BATCH,             // CTRL_CANNY_BATCH=n: hysteresis passes of the canny extractor enqueued per flag readback (1..16)
     P_COUNT
 };
 // the variable's value as getenv() would return it (nullptr = unset), from the table: environment snapshot or ctrl_policy_set override

@@ -342,6 +342,26 @@ int ctrl_op_conv3x3_small_mfma(const void* x, const void* w, const float* bias, 
 int ctrl_prepare_images(const void* src_u8, int F, int Hin, int Win, const int32_t* hbounds, const int32_t* hk, int hks,
                         const int32_t* vbounds, const int32_t* vk, int vks, void* tmp_u8, void* out, int out_dtype,
                         int W, int H, int repeat, int cfg, void* stream);
+/* Canny condition extraction (model/ctrl_helper.py:171-179: cv2.Canny(np.array(img), 100, 200), then the edge map three times along the
+ * channel axis), bit for bit OpenCV's Canny with apertureSize 3 and the L1 magnitude, for N images of one size in one call.
+ *   src_u8 uint8 [N][H][W][C], C = 1 | 3 (device; any byte alignment); low / high as cv2 takes them: swapped when low > high, then floored
+ *   map    uint8 [N][H][W]: 0 no candidate, 1 weak, 2 strong (ctrl_op_canny_map writes it, ctrl_op_canny_hysteresis promotes every weak
+ *          pixel 8-connected to a strong one, ctrl_op_canny_finish turns it into 0 / 255 as [N][H][W] (out_channels 1) or [N][H][W][3])
+ *   ws     device scratch, 4-byte aligned: ctrl_canny_ws_bytes(N, H, W) bytes for ctrl_canny (a 256-byte flag block, then the map);
+ *          ctrl_op_canny_hysteresis uses the flag block only
+ *   *passes    hysteresis passes up to and including the first that promoted nothing; *readbacks  flag readbacks (each a stream
+ *          synchronisation; CTRL_CANNY_BATCH passes are enqueued per readback)
+ * The hysteresis loop reads a flag back between launches: ctrl_op_canny_hysteresis and ctrl_canny refuse a capturing stream.  Every entry
+ * returns non-zero (ctrl_last_error) for a null pointer, C or out_channels outside {1, 3}, N, H or W < 1, and N*H*W*3 beyond 2^31 - 1 bytes
+ * (ctrl_canny_ws_bytes returns 0 for such sizes).  ctrl_canny_launch_shape: the tile (pixels) one workgroup of the map and of the hysteresis
+ * kernel owns -- where the tests put their edges. */
+int ctrl_op_canny_map(const void* src_u8, int N, int H, int W, int C, double low, double high, void* map, void* stream);
+int ctrl_op_canny_hysteresis(void* map, int N, int H, int W, void* ws, int64_t ws_bytes, int* passes, int* readbacks, void* stream);
+int ctrl_op_canny_finish(const void* map, int N, int H, int W, int out_channels, void* out, void* stream);
+int ctrl_canny(const void* src_u8, int N, int H, int W, int C, double low, double high, int out_channels, void* out, void* ws,
+               int64_t ws_bytes, int* passes, int* readbacks, void* stream);
+int64_t ctrl_canny_ws_bytes(int N, int H, int W);
+int ctrl_canny_launch_shape(int H, int W, int* tile_h, int* tile_w);
 /* load-time packers */
 int ctrl_op_pack_conv_w(const void* w, int dtype, void* out, int Cout, int Cin, int taps, void* stream);
 /* weights of a split-operand convolution: [Cout][taps][2*Cin], every tap's Cin weights twice (for the hi and the lo half) */
