@@ -184,7 +184,7 @@ class ClipComm(C.Structure):
 
 
 # every symbol include/ctrl_hip.h declares (tests check the library exports all of them)
-ABI_VERSION = 10      # CTRL_ABI_VERSION of include/ctrl_hip.h
+ABI_VERSION = 11     # CTRL_ABI_VERSION of include/ctrl_hip.h
 EXPORTS = [
     "ctrl_abi_version", "ctrl_last_error", "ctrl_prof_begin", "ctrl_prof_end", "ctrl_prof_count", "ctrl_prof_get",
     "ctrl_prof_launch_count", "ctrl_prof_launch_get",
@@ -216,7 +216,7 @@ EXPORTS = [
     "ctrl_vae_tdecoder_param_count", "ctrl_vae_tdecoder_param_spec", "ctrl_vae_tdecoder_create", "ctrl_vae_tdecoder_destroy",
     "ctrl_vae_tdecoder_forward", "ctrl_op_vae_time_conv",
     "ctrl_unet_st_param_count", "ctrl_unet_st_param_spec", "ctrl_unet_st_create", "ctrl_unet_st_destroy", "ctrl_unet_st_selection",
-    "ctrl_unet_st_forward", "ctrl_op_unet_skip_join",
+    "ctrl_unet_st_forward", "ctrl_op_unet_skip_join", "ctrl_op_unet_skip_join_split",
     "ctrl_unet2d_param_count", "ctrl_unet2d_param_spec", "ctrl_unet2d_create", "ctrl_unet2d_destroy", "ctrl_unet2d_selection",
     "ctrl_unet2d_set_text_cache", "ctrl_unet2d_forward", "ctrl_unet2d_workspace_bytes", "ctrl_op_unet_text_time",
     "ctrl_unet_i2v_param_count", "ctrl_unet_i2v_param_spec", "ctrl_unet_i2v_create", "ctrl_unet_i2v_destroy", "ctrl_unet_i2v_selection",
@@ -320,6 +320,8 @@ def lib():
                                               C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _lib.ctrl_op_unet_skip_join.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                 C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
+        _lib.ctrl_op_unet_skip_join_split.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                      C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]
         _lib.ctrl_unet2d_destroy.restype = None
         _lib.ctrl_unet2d_destroy.argtypes = [C.c_void_p]
         _lib.ctrl_unet2d_set_text_cache.argtypes = [C.c_void_p, C.c_int]

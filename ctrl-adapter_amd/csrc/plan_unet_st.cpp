@@ -556,4 +556,10 @@ int ctrl_op_unet_skip_join(const float* skip, int64_t ld_skip, const void* res, 
     return op_unet_skip_join(skip, (long)ld_skip, res, res_dtype, res_5d, B, F, HW, C2, out32, (half_t*)out16, (long)ld_out, col, S(stream));
 }
 
+int ctrl_op_unet_skip_join_split(const float* skip, int64_t ld_skip, const void* res, int res_dtype, int res_5d, int B, int F, int HW, int C2,
+                                 float* out32, void* out16, int64_t ld_out, int col, int lo_off, void* stream) {
+    return op_unet_skip_join(skip, (long)ld_skip, res, res_dtype, res_5d, B, F, HW, C2, out32, (half_t*)out16, (long)ld_out, col, S(stream),
+                             lo_off);
+}
+
 }  // extern "C"

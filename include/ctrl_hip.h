@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define CTRL_ABI_VERSION 10
+#define CTRL_ABI_VERSION 11
 
 /* element types of boundary tensors */
 enum { CTRL_F32 = 0, CTRL_F16 = 1, CTRL_BF16 = 2 };
@@ -874,6 +874,12 @@ int ctrl_unet_st_forward(ctrl_unet_st* h, const void* sample, int sample_dtype, 
    ld_out elements.  res (may be NULL): (b f) c h w (res_5d = 0) or b c f h w (res_5d = 1) in res_dtype.  skip may be out32 with col = 0. */
 int ctrl_op_unet_skip_join(const float* skip, int64_t ld_skip, const void* res, int res_dtype, int res_5d, int B, int F, int HW, int C2,
                            float* out32, void* out16, int64_t ld_out, int col, void* stream);
+/* Test ABI (tests/shell_forms.py, tests/test_gpu_shell_forms.py): the form the SDXL and I2VGen-XL plans launch.
+   The same with a split mirror (lo_off != 0; lo_off = 0 is the call above): out16 rows are 2 * ld_out halves wide, hi = fp16(v) at
+   [col, col + C2) and lo = fp16(v - hi) at lo_off + [col, col + C2).  lo_off a multiple of 8, at least col + C2, lo_off + col + C2 <=
+   2 * ld_out; needs out16. */
+int ctrl_op_unet_skip_join_split(const float* skip, int64_t ld_skip, const void* res, int res_dtype, int res_5d, int B, int F, int HW, int C2,
+                                 float* out32, void* out16, int64_t ld_out, int col, int lo_off, void* stream);
 
 /* ---- SDXL backbone UNet (diffusers UNet2DConditionModel, addition_embed_type "text_time", linear transformer projections) ---- */
 typedef struct ctrl_unet2d_config {

@@ -36,7 +36,10 @@ def test_library_exports_every_declared_symbol():
     # per-pixel kernels only a plan reached (tests/helper_forms.py, tests/test_gpu_helper_forms.py)
     assert {"ctrl_op_pack_conv_w_ovf", "ctrl_op_pack_conv_w_dup_ovf", "ctrl_op_pack_conv_w_phase_ovf", "ctrl_op_pack_linear_w_ovf",
             "ctrl_op_nhwc_to_nchw_map", "ctrl_op_unet_conv_out", "ctrl_op_i2v_frames", "ctrl_op_vae_conv_in"} <= declared
-    assert lib.ctrl_abi_version() == _lib.ABI_VERSION == 10
+    # the test ABI of the VAE and UNet shell kernels: the skip join with a split mirror, which only a plan reached (tests/shell_forms.py,
+    # tests/test_gpu_shell_forms.py)
+    assert "ctrl_op_unet_skip_join_split" in declared
+    assert lib.ctrl_abi_version() == _lib.ABI_VERSION == 11
 
 
 def test_struct_sizes_match_header():

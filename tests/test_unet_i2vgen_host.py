@@ -74,7 +74,7 @@ def test_config_struct_size_matches_the_header_and_symbols_resolve(tmp_path):
                  "ctrl_unet_i2v_set_cond_cache", "ctrl_unet_i2v_forward", "ctrl_unet_i2v_workspace_bytes", "ctrl_op_i2v_latent_encoder",
                  "ctrl_op_adaptive_avgpool_nhwc"):
         assert hasattr(lib, name) and name in _lib.EXPORTS
-    assert _lib.ABI_VERSION == 10 and lib.ctrl_abi_version() == 10
+    assert _lib.ABI_VERSION == 11 and lib.ctrl_abi_version() == 11
 
 
 def test_forward_signature_is_the_references():

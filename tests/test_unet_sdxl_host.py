@@ -106,7 +106,7 @@ def test_config_struct_size_matches_the_header_and_symbols_resolve(tmp_path):
     for name in ("ctrl_unet2d_param_count", "ctrl_unet2d_param_spec", "ctrl_unet2d_create", "ctrl_unet2d_destroy", "ctrl_unet2d_selection",
                  "ctrl_unet2d_set_text_cache", "ctrl_unet2d_forward", "ctrl_unet2d_workspace_bytes", "ctrl_op_unet_text_time"):
         assert hasattr(lib, name) and name in _lib.EXPORTS
-    assert _lib.ABI_VERSION == 10 and lib.ctrl_abi_version() == 10
+    assert _lib.ABI_VERSION == 11 and lib.ctrl_abi_version() == 11
 
 
 # every key of SDXL-base's unet/config.json (diffusers 0.19), with the widths of LPB1

@@ -69,7 +69,7 @@ def test_config_struct_size_matches_the_header_and_symbols_resolve(tmp_path):
     for name in ("ctrl_unet_st_param_count", "ctrl_unet_st_param_spec", "ctrl_unet_st_create", "ctrl_unet_st_destroy", "ctrl_unet_st_selection",
                  "ctrl_unet_st_forward", "ctrl_op_unet_skip_join"):
         assert hasattr(lib, name) and name in _lib.EXPORTS
-    assert _lib.ABI_VERSION == 10 and lib.ctrl_abi_version() == 10
+    assert _lib.ABI_VERSION == 11 and lib.ctrl_abi_version() == 11
 
 
 def test_state_dict_and_save_pretrained_round_trip(tmp_path):

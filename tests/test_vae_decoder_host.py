@@ -135,9 +135,9 @@ def test_config_struct_matches_header_and_abi_version():
         open(os.path.join(d, "s.c"), "w").write(src)
         subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "s.c"), "-o", os.path.join(d, "s")])
         out = subprocess.check_output([os.path.join(d, "s")]).decode().split()
-    assert [int(v) for v in out] == [ctypes.sizeof(_lib.VaeDecoderConfig), 10]
+    assert [int(v) for v in out] == [ctypes.sizeof(_lib.VaeDecoderConfig), 11]
     assert _lib.VaeDecoderConfig.out_channels.offset == _lib.VaeDecoderConfig.norm_eps.offset + 4
-    assert _lib.ABI_VERSION == 10 and _lib.lib().ctrl_abi_version() == 10
+    assert _lib.ABI_VERSION == 11 and _lib.lib().ctrl_abi_version() == 11
     assert (_lib.VAE_DEC_SAMPLE, _lib.VAE_DEC_UNIT, _lib.VAE_DEC_U8) == (0, 1, 2)
 
 

@@ -45,7 +45,7 @@ def test_new_symbols_resolve_and_abi_version_stays():
     for name in ("ctrl_vae_tdecoder_param_count", "ctrl_vae_tdecoder_param_spec", "ctrl_vae_tdecoder_create", "ctrl_vae_tdecoder_destroy",
                  "ctrl_vae_tdecoder_forward", "ctrl_op_vae_time_conv"):
         assert hasattr(lib, name) and name in _lib.EXPORTS
-    assert _lib.ABI_VERSION == 10 and lib.ctrl_abi_version() == 10
+    assert _lib.ABI_VERSION == 11 and lib.ctrl_abi_version() == 11
 
 
 def test_state_dict_and_save_pretrained_round_trip(tmp_path):

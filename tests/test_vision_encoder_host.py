@@ -207,7 +207,7 @@ def test_vision_abi_symbols_resolve():
                  "ctrl_vision_encoder_destroy", "ctrl_vision_encoder_forward", "ctrl_op_vision_patchify", "ctrl_op_vision_embed",
                  "ctrl_op_vision_cls_ln", "ctrl_op_clip_resize_aa"):
         assert hasattr(lib, name), name
-    assert lib.ctrl_abi_version() == 10
+    assert lib.ctrl_abi_version() == 11
     cfg = _lib.VisionEncoderConfig()
     cfg.image_size, cfg.patch_size, cfg.hidden_size, cfg.intermediate_size = 224, 14, 1280, 5120
     cfg.num_hidden_layers, cfg.num_attention_heads, cfg.projection_dim, cfg.hidden_act, cfg.layer_norm_eps = 32, 16, 1024, 1, 1e-5
