@@ -168,6 +168,10 @@ SAMPLER_ROW = 8       # CTRL_SAMPLER_ROW: c_in, A, B, t_model, t_aux0, t_aux1, 0
 VAE_DEC_SAMPLE, VAE_DEC_UNIT, VAE_DEC_U8 = 0, 1, 2      # epilogues of ctrl_vae_decoder_forward / ctrl_op_vae_dec_tail
 
 
+class HedConfig(C.Structure):
+    _fields_ = [("trunk_scale", C.c_float), ("reserved", C.c_int32), ("ws_cap_bytes", C.c_int64)]
+
+
 U8_NHWC = 3     # pixel dtype of ctrl_vision_encoder_forward / the vision ops: uint8 [N][H][W][3]
 
 
@@ -228,6 +232,8 @@ EXPORTS = [
     "ctrl_op_pack_conv_w_ovf", "ctrl_op_pack_conv_w_dup_ovf", "ctrl_op_pack_conv_w_phase_ovf", "ctrl_op_pack_linear_w_ovf",
     "ctrl_op_nhwc_to_nchw_map", "ctrl_op_unet_conv_out", "ctrl_op_i2v_frames", "ctrl_op_vae_conv_in",
     "ctrl_op_canny_map", "ctrl_op_canny_hysteresis", "ctrl_op_canny_finish", "ctrl_canny", "ctrl_canny_ws_bytes", "ctrl_canny_launch_shape",
+    "ctrl_hed_create", "ctrl_hed_destroy", "ctrl_hed_forward", "ctrl_hed_ws_bytes", "ctrl_op_hed_stem", "ctrl_op_hed_pool_proj",
+    "ctrl_op_hed_fuse", "ctrl_op_hed_blur_f32", "ctrl_op_hed_nms", "ctrl_op_hed_blur_u8_bin",
 ]
 
 _lib = None
@@ -249,7 +255,7 @@ def lib():
                             "ctrl_text_encoder_destroy", "ctrl_vision_encoder_destroy", "ctrl_vae_encoder_destroy", "ctrl_vae_decoder_destroy",
                             "ctrl_vae_tdecoder_destroy", "ctrl_unet_st_destroy", "ctrl_unet2d_destroy", "ctrl_unet2d_workspace_bytes",
                             "ctrl_unet_i2v_destroy", "ctrl_unet_i2v_workspace_bytes", "ctrl_sampler_destroy", "ctrl_sampler_scalars",
-                            "ctrl_canny_ws_bytes"):
+                            "ctrl_canny_ws_bytes", "ctrl_hed_destroy", "ctrl_hed_ws_bytes"):
                 fn.restype = C.c_int
         _lib.ctrl_policy_get.restype = C.c_char_p
         _lib.ctrl_policy_get.argtypes = [C.c_char_p]
@@ -379,6 +385,21 @@ def lib():
         _lib.ctrl_canny_ws_bytes.restype = C.c_int64
         _lib.ctrl_canny_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
         _lib.ctrl_canny_launch_shape.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        _lib.ctrl_hed_create.argtypes = [C.POINTER(HedConfig), C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
+        _lib.ctrl_hed_destroy.restype = None
+        _lib.ctrl_hed_destroy.argtypes = [C.c_void_p]
+        _lib.ctrl_hed_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                          C.c_void_p]
+        _lib.ctrl_hed_ws_bytes.restype = C.c_int64
+        _lib.ctrl_hed_ws_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+        _lib.ctrl_op_hed_stem.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_float,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ctrl_op_hed_pool_proj.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]
+        _lib.ctrl_op_hed_fuse.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ctrl_op_hed_blur_f32.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.ctrl_op_hed_nms.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.ctrl_op_hed_blur_u8_bin.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _lib.ctrl_rccl_comm_destroy.restype = None
         _lib.ctrl_rccl_comm_destroy.argtypes = [C.c_void_p]
         _lib.ctrl_rccl_comm_bytes_sent.restype = C.c_int64

@@ -86,7 +86,12 @@ __device__ __forceinline__ float silu_f(float x) { return x * __builtin_amdgcn_r
 // x * sigmoid(k x) in the rcp / exp form of silu_f: the GEMM epilogue activations (ctrl_igemm_desc::act) 1 = SiLU (k = 1: -k * x is
 // exactly -x, the same value as silu_f) and 2 = quick_gelu (CLIP's hidden_act, k = 1.702) share one code path
 __device__ __forceinline__ float x_sigmoid_kx(float x, float k) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-k * x)); }
-__device__ __forceinline__ float act_k(int act) { return act == 2 ? 1.702f : 1.0f; }
+// 3 = ReLU (the HED trunk) on the SAME code path, as the limit k -> inf: with k = 3e38, exp(-k x) is exactly 0 for every
+// x >= 2^-120 (the result is x * rcp(1) = x bit for bit) and +inf for every x <= -2^-120 (x * rcp(inf) = x * 0 = -0); x = +-0 gives 0, a NaN
+// stays a NaN and -inf becomes one (the range check sees both), +inf stays.  Only 0 < x < 2^-120 -- far below the smallest fp16
+// subnormal -- comes out between x / 2 and x.  A select beside the sigmoid form was built first: it cost the 8-phase and the 256 x 320
+// kernels scratch and VGPR spills; this form adds one scalar select to act_k and nothing to the epilogues.
+__device__ __forceinline__ float act_k(int act) { return act == 2 ? 1.702f : (act == 3 ? 3.0e38f : 1.0f); }
 // exact (erf) GELU with erf from Abramowitz-Stegun 7.1.26 (|abs error| <= 1.5e-7, far below fp16 resolution).
 //   gelu(x) = x/2 * (1 + erf(x/sqrt2)),  erf(z) = sign(z) * (1 - P(t) e^{-z^2}),  t = 1/(1 + p|z|)
 //           = max(x, 0) - |x| * (P(t)/2) * e^{-x^2/2}            (x/2 + |x|/2 = max(x,0): no sign select, no 1 +/- erf)

@@ -367,9 +367,28 @@ int op_canny_finish(const unsigned char* map, int N, int H, int W, int out_chann
 int op_canny(const unsigned char* src, int N, int H, int W, int C, double low, double high, int out_channels, unsigned char* out,
              void* ws, long ws_bytes, int* passes, int* readbacks, hipStream_t s);
 
+// ------------------------------------------------------------------------------------------
+// HED annotator (hed.hip; controlnet_aux HEDdetector: the `scribble` branch of model/ctrl_helper.py:196-197 and the soft-edge condition)
+//   stem: src uint8 [N][H][W][3] -> relu(conv3x3((x - norm3) * scale) + bias) fp16 [N][H][W][64]; w fp32 [9][3][64]
+//   (op_pack_conv_w_direct), bias [64] (already multiplied by scale), norm3 on the HOST; nonfinite (optional): raised when a value leaves fp16
+//   pool_proj: h fp16 [N][H][W][C] -> p fp32 [N][H][W] = inv_scale * (h . wp) + bp[0] and, when pooled is given, max_pool2d(2, 2) of h
+//   fuse: maps5 (host array of five device maps, fp32 [N][H >> k][W >> k]) -> cv2 INTER_LINEAR to H x W, mean (logits, optional fp32
+//   [N][H][W]), sigmoid, * 255, clip, truncate -> uint8 [N][H][W] | [N][H][W][3]
+//   blur_f32 / nms / blur_u8_bin: the scribble tail at sigma 3 (25 taps to fp32; threshold 127; 19 taps to uint8, > 4 -> 255 else 0),
+//   bit for bit tests/hed_ref.py
+// ------------------------------------------------------------------------------------------
+int op_hed_stem(const unsigned char* src, int N, int H, int W, const float* w, const float* bias, const float* norm3, float scale, half_t* out,
+                int32_t* nonfinite, hipStream_t s);
+int op_hed_pool_proj(const half_t* h, int N, int H, int W, int C, const float* wp, const float* bp, float inv_scale, half_t* pooled, float* p,
+                     hipStream_t s);
+int op_hed_fuse(const float* const* maps5, int N, int H, int W, int out_channels, unsigned char* out, float* logits, hipStream_t s);
+int op_hed_blur_f32(const unsigned char* src, int N, int H, int W, float* out, hipStream_t s);
+int op_hed_nms(const float* x, int N, int H, int W, unsigned char* out, hipStream_t s);
+int op_hed_blur_u8_bin(const unsigned char* src, int N, int H, int W, int out_channels, unsigned char* out, hipStream_t s);
+int op_hed_scale_vec(float* v, int n, float scale, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
-// Grouped launches over sibling problems (round 5).  The adapter blocks of one pyramid level are independent and have identical
+// Grouped launches over sibling problems (round 5). The adapter blocks of one pyramid level are independent and have identical
 // shapes (model/ctrl_adapter.py:181-191 simply runs them one after the other): the plan records the op sequence of every sibling and
 // replays the sequences in lock-step; while a collector is installed, the ops below deposit their arguments instead of launching,
 // and flush() launches what was deposited for one step -- as ONE grouped launch when the problems agree in shape and form,

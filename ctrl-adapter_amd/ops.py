@@ -81,7 +81,7 @@ def pack_vec(v, geglu=False):
 def igemm(A, lda, W, M, Nout, Cin, taps=1, mode=IG_ROWS, geom=None, bias=None, rowvec=None, rows_per_img=1,
           res=None, ldres=0, scale=1.0, geglu=False, segs=None, F=0, HW=0, out16=None, ld16=0, splitk_ws=None,
           blend_mix=None, blend_x=None, ld_blend=0, a_split=False, out16_lo_off=0, t_pad=False, scale2=0.0, scale2_from=0,
-          res_up=0, scale2_to=0, tap_origin=0, pinned=False, splitk_tickets=None):
+          res_up=0, scale2_to=0, tap_origin=0, pinned=False, splitk_tickets=None, act=0):
     """segs: list of (out_tensor, ld, col_begin, ncols, fmt, L); res_up=2: `res` is [N][Hout/2][Wout/2][ldres], read through a
     nearest x2 up-sampling (conv2d); pinned: the encoder plans' fixed 64 x 64 x 64 form (op_igemm_pinned) instead of the dispatcher;
     splitk_tickets: zeroed int32 ticket words of the in-launch split-K reduction (None: the library zeroes its own)"""
@@ -115,7 +115,7 @@ def igemm_select(d, group_n=1, pinned=False):
 def igemm_desc(A, lda, W, M, Nout, Cin, taps=1, mode=IG_ROWS, geom=None, bias=None, rowvec=None, rows_per_img=1,
                res=None, ldres=0, scale=1.0, geglu=False, segs=None, F=0, HW=0, out16=None, ld16=0, splitk_ws=None,
                blend_mix=None, blend_x=None, ld_blend=0, a_split=False, out16_lo_off=0, t_pad=False, scale2=0.0, scale2_from=0,
-               res_up=0, scale2_to=0, tap_origin=0, splitk_tickets=None):
+               res_up=0, scale2_to=0, tap_origin=0, splitk_tickets=None, act=0):
     """the ctrl_igemm_desc of ops.igemm's arguments (the tensors must stay alive while it is used)"""
     d = L.IGemmDesc()
     d.A = A.data_ptr(); d.lda = lda; d.mode = mode; d.Cin = Cin; d.taps = taps
@@ -141,7 +141,7 @@ def igemm_desc(A, lda, W, M, Nout, Cin, taps=1, mode=IG_ROWS, geom=None, bias=No
     d.blend_x = blend_x.data_ptr() if blend_x is not None else None
     d.ld_blend = ld_blend
     d.blend_f32 = int(blend_x is not None and blend_x.dtype == torch.float32)
-    d.scale = scale; d.geglu = int(geglu)
+    d.scale = scale; d.geglu = int(geglu); d.act = int(act)      # act: 0 none, 1 SiLU, 2 quick_gelu, 3 ReLU
     d.scale2 = scale2; d.scale2_from = scale2_from; d.scale2_to = scale2_to
     d.a_split = int(a_split); d.out16_lo_off = out16_lo_off      # a_split: 0 | 1 (weights packed twice) | 2 (paired walk)
     d.nseg = len(segs)

@@ -93,7 +93,8 @@ typedef struct ctrl_igemm_desc {
     float scale;
     int32_t geglu;      /* weights packed in interleaved (hidden,gate) 16-column blocks; out width Nout/2 */
     int32_t nseg;
-    int32_t act;        /* 0 none, 1 SiLU, 2 quick_gelu x*sigmoid(1.702x) (CLIP's MLP); applied after bias/rowvec (before residual) */
+    int32_t act;        /* 0 none, 1 SiLU, 2 quick_gelu x*sigmoid(1.702x) (CLIP's MLP), 3 ReLU (the HED trunk: a negative value becomes
+                           a zero, a value of at least 2^-120 is kept bit for bit); applied after bias/rowvec (before residual) */
     int32_t res_f32;    /* residual is fp32 (the fp32 residual stream) */
     int32_t a_split;    /* split operand: A rows hold [hi | lo] fp16 halves of an fp32 operand along Cin (lo = fp16(x - hi)), so the
                            product is exact in A to ~2^-22 at twice the MFMA work (the ControlNet's convolutions).
@@ -832,7 +833,57 @@ int ctrl_vae_tdecoder_forward(ctrl_vae_tdecoder* h, const void* latents, int lat
 int ctrl_op_vae_time_conv(const float* x, const float* w, const float* b, int F, int H, int W, int Cout, int kind, void* out,
                           int out_dtype, void* stream);
 
-/* ---- SVD backbone UNet (diffusers UNetSpatioTemporalConditionModel with the reference's two ControlNet-residual kwargs) ---- */
+/* ---- HED annotator (controlnet_aux ControlNetHED_Apache2 + HEDdetector): the reference's `scribble` condition
+ * (model/ctrl_helper.py:124-127, 196-197: HEDdetector(img, scribble=True)) and ControlNet's soft-edge condition (scribble = 0) ----
+ * Parameters by controlnet_aux's state-dict keys: norm [1][3][1][1], blockK.convs.J.weight / .bias (K = 1..5; 2, 2, 3, 3, 3 convs of
+ * 64, 128, 256, 512, 512 channels), blockK.projection.weight [1][C][1][1] / .bias [1].
+ *   trunk_scale  a power of two s (default 1): the trunk runs on s * activations -- the stem multiplies (x - norm) by s, every trunk bias
+ *                is multiplied by s once at creation, every projection multiplies by 1 / s before its bias; exact in the fp32
+ *                accumulators, it moves the fp16 activations of a checkpoint with large activations (the input is 0..255) back into
+ *                range.  A forward whose activations leave the fp16 range anyway returns an error (it reads one flag word back at
+ *                its end, so it synchronises its stream and refuses a capturing one).
+ *   ws_cap_bytes the workspace one group of frames may take (0 = 1 GiB): the frames of a call run in equal groups of the largest size
+ *                that stays below it (one 512 x 512 frame needs about 70 MB), or in groups of frames_per_group when that is positive.
+ *                A frame's result does not depend on the group it ran in.
+ * ctrl_hed_forward: frames uint8 [N][H][W][3] (device), H and W multiples of 64 -> out uint8 [N][H][W] (out_channels 1) or
+ * [N][H][W][3]: the soft edge map, or with scribble != 0 the map after nms(127, 3.0), GaussianBlur(sigma 3) and the binarisation;
+ * logits (optional, device fp32 [N][H][W]): the mean of the five resized side outputs in front of the sigmoid.
+ * ctrl_hed_ws_bytes: the workspace that forward would reserve (0 for arguments it would refuse). */
+typedef struct ctrl_hed_config {
+    float trunk_scale;
+    int32_t reserved;
+    int64_t ws_cap_bytes;
+} ctrl_hed_config;
+typedef struct ctrl_hed ctrl_hed;   /* opaque */
+int ctrl_hed_create(const ctrl_hed_config* cfg, const ctrl_tensor_ref* tensors, int n_tensors, void* stream, ctrl_hed** out);
+void ctrl_hed_destroy(ctrl_hed* h);
+int ctrl_hed_forward(ctrl_hed* h, const void* frames_u8, int N, int H, int W, int scribble, int out_channels, void* out_u8, float* logits,
+                     int frames_per_group, void* stream);
+int64_t ctrl_hed_ws_bytes(ctrl_hed* h, int N, int H, int W, int scribble, int frames_per_group);
+/* op level (csrc/hed.hip), the kernels around the trunk's implicit GEMMs (ctrl_igemm_desc::act = 3):
+ *   stem       src uint8 [N][H][W][3] -> relu(conv3x3((x - norm) * scale, w) + bias) fp16 [N][H][W][64]; w fp32 [9][3][64]
+ *              (ctrl_op_pack_conv_w_direct), bias fp32 [64] as it is added (the plan hands in scale * bias), norm: three floats on the
+ *              HOST; the zero padding applies to x - norm; nonfinite (optional, device): set to 1 when an output leaves fp16; W % 4 == 0
+ *   pool_proj  h fp16 [N][H][W][C] (C = 64 | 128 | 256 | 512, H and W even) -> p fp32 [N][H][W] = inv_scale * (h . wp) + bp[0] and,
+ *              when pooled is not NULL, max_pool2d(h, 2, 2) fp16 [N][H/2][W/2][C]; wp fp32 [C], bp fp32 [1] (device)
+ *   fuse       maps: HOST array of five device pointers, map k fp32 [N][H >> k][W >> k] -> cv2.resize(INTER_LINEAR) to H x W (float32,
+ *              fx = (dx + 0.5) * scale - 0.5, clamped at both borders, rows interpolated along x first), the mean of the five (logits,
+ *              optional fp32 [N][H][W]), uint8(clip(sigmoid * 255)) by truncation into out [N][H][W] | [N][H][W][3]; H, W % 16 == 0
+ *   blur_f32   uint8 [N][H][W] -> fp32: cv2.GaussianBlur(x.astype(float32), (0, 0), 3.0), 25 taps, BORDER_REFLECT_101
+ *   nms        fp32 [N][H][W] -> uint8: 255 where cv2.dilate(x, f) == x for one of the four 3-pixel line kernels and x > 127, else 0
+ *   blur_u8_bin uint8 [N][H][W] -> cv2.GaussianBlur(x, (0, 0), 3.0) on uint8 (19 taps), then > 4 -> 255, else 0, on out_channels channels
+ * The three tail kernels reproduce tests/hed_ref.py bit for bit: taps normalised in double and cast to float, every tap one rounded
+ * multiply and one rounded add in fp32 from left to right, the row pass before the column pass. */
+int ctrl_op_hed_stem(const void* src_u8, int N, int H, int W, const float* w, const float* bias, const float* norm_host3, float scale,
+                     void* out_f16, int32_t* nonfinite, void* stream);
+int ctrl_op_hed_pool_proj(const void* h_f16, int N, int H, int W, int C, const float* wp, const float* bp, float inv_scale, void* pooled_f16,
+                          float* p, void* stream);
+int ctrl_op_hed_fuse(const float* const* maps, int N, int H, int W, int out_channels, void* out_u8, float* logits, void* stream);
+int ctrl_op_hed_blur_f32(const void* src_u8, int N, int H, int W, float* out, void* stream);
+int ctrl_op_hed_nms(const float* x, int N, int H, int W, void* out_u8, void* stream);
+int ctrl_op_hed_blur_u8_bin(const void* src_u8, int N, int H, int W, int out_channels, void* out_u8, void* stream);
+
+/* ---- SVD backbone UNet(diffusers UNetSpatioTemporalConditionModel with the reference's two ControlNet-residual kwargs) ---- */
 typedef struct ctrl_unet_st_config {
     int32_t in_channels;                           /* 8 */
     int32_t out_channels;                          /* 1..4 */
