@@ -172,6 +172,10 @@ class HedConfig(C.Structure):
     _fields_ = [("trunk_scale", C.c_float), ("reserved", C.c_int32), ("ws_cap_bytes", C.c_int64)]
 
 
+class PidiConfig(C.Structure):
+    _fields_ = [("frames_per_group", C.c_int32), ("reserved", C.c_int32), ("ws_cap_bytes", C.c_int64)]
+
+
 U8_NHWC = 3     # pixel dtype of ctrl_vision_encoder_forward / the vision ops: uint8 [N][H][W][3]
 
 
@@ -234,6 +238,9 @@ EXPORTS = [
     "ctrl_op_canny_map", "ctrl_op_canny_hysteresis", "ctrl_op_canny_finish", "ctrl_canny", "ctrl_canny_ws_bytes", "ctrl_canny_launch_shape",
     "ctrl_hed_create", "ctrl_hed_destroy", "ctrl_hed_forward", "ctrl_hed_ws_bytes", "ctrl_op_hed_stem", "ctrl_op_hed_pool_proj",
     "ctrl_op_hed_fuse", "ctrl_op_hed_blur_f32", "ctrl_op_hed_nms", "ctrl_op_hed_blur_u8_bin",
+    "ctrl_pidi_create", "ctrl_pidi_destroy", "ctrl_pidi_forward", "ctrl_pidi_ws_bytes", "ctrl_pidi_convert_pdc", "ctrl_pidi_launch_shape",
+    "ctrl_op_pidi_stem", "ctrl_op_pidi_block", "ctrl_op_pidi_head_reduce", "ctrl_op_pidi_head_context", "ctrl_op_pidi_side",
+    "ctrl_op_pidi_fuse",
 ]
 
 _lib = None
@@ -255,7 +262,7 @@ def lib():
                             "ctrl_text_encoder_destroy", "ctrl_vision_encoder_destroy", "ctrl_vae_encoder_destroy", "ctrl_vae_decoder_destroy",
                             "ctrl_vae_tdecoder_destroy", "ctrl_unet_st_destroy", "ctrl_unet2d_destroy", "ctrl_unet2d_workspace_bytes",
                             "ctrl_unet_i2v_destroy", "ctrl_unet_i2v_workspace_bytes", "ctrl_sampler_destroy", "ctrl_sampler_scalars",
-                            "ctrl_canny_ws_bytes", "ctrl_hed_destroy", "ctrl_hed_ws_bytes"):
+                            "ctrl_canny_ws_bytes", "ctrl_hed_destroy", "ctrl_hed_ws_bytes", "ctrl_pidi_destroy", "ctrl_pidi_ws_bytes"):
                 fn.restype = C.c_int
         _lib.ctrl_policy_get.restype = C.c_char_p
         _lib.ctrl_policy_get.argtypes = [C.c_char_p]
@@ -400,6 +407,25 @@ def lib():
         _lib.ctrl_op_hed_blur_f32.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _lib.ctrl_op_hed_nms.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _lib.ctrl_op_hed_blur_u8_bin.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.ctrl_pidi_create.argtypes = [C.POINTER(PidiConfig), C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
+        _lib.ctrl_pidi_destroy.restype = None
+        _lib.ctrl_pidi_destroy.argtypes = [C.c_void_p]
+        _lib.ctrl_pidi_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                           C.c_int, C.c_void_p]
+        _lib.ctrl_pidi_ws_bytes.restype = C.c_int64
+        _lib.ctrl_pidi_ws_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+        _lib.ctrl_pidi_convert_pdc.argtypes = [C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_float)]
+        _lib.ctrl_pidi_launch_shape.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        _lib.ctrl_op_pidi_stem.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ctrl_op_pidi_block.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ctrl_op_pidi_head_reduce.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]
+        _lib.ctrl_op_pidi_head_context.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_void_p, C.c_void_p,
+                                                   C.c_void_p]
+        _lib.ctrl_op_pidi_side.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
+        _lib.ctrl_op_pidi_fuse.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]
         _lib.ctrl_rccl_comm_destroy.restype = None
         _lib.ctrl_rccl_comm_destroy.argtypes = [C.c_void_p]
         _lib.ctrl_rccl_comm_bytes_sent.restype = C.c_int64

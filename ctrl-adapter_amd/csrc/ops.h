@@ -388,6 +388,24 @@ int op_hed_blur_u8_bin(const unsigned char* src, int N, int H, int W, int out_ch
 int op_hed_scale_vec(float* v, int n, float scale, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
+// PiDiNet annotator (pidinet.hip; controlnet_aux PidiNetDetector: the `softedge` branch of model/ctrl_helper.py:103-107, 184-185).
+// Layouts and semantics: include/ctrl_hip.h (ctrl_op_pidi_*).  fp16 NHWC activations, channels padded to a multiple of 64 (pidi_cp).
+// ------------------------------------------------------------------------------------------
+inline int pidi_cp(int C) { return (C + 63) & ~63; }
+constexpr int kPidiHeadC = 24, kPidiHeadCP = 32, kPidiHeadTaps = 36;
+void pidi_launch_shape(int kernel, int* tile_h, int* tile_w);
+int pidi_convert_pdc(int kind, const float* w, int Co, int Ci, float* out);      // host only
+int op_pidi_stem(const unsigned char* src, int N, int H, int W, const float* w, half_t* out, int32_t* nonfinite, hipStream_t s);
+int op_pidi_block(const half_t* x, int N, int H, int W, int Cin, int Cout, int taps, const float* dw, const half_t* w2, const half_t* wsc,
+                  const float* bsc, int pool, half_t* out, int32_t* nonfinite, hipStream_t s);
+int op_pidi_head_reduce(const half_t* x, int N, int H, int W, int C, const half_t* w1, const float* b1, half_t* t, int32_t* nonfinite,
+                        hipStream_t s);
+int op_pidi_head_context(const half_t* t, int N, int H, int W, const half_t* wd, const float* par124, float* a4, float* d, hipStream_t s);
+int op_pidi_side(const float* a4, const float* d, int N, int H, int W, const float* par37, float* e, hipStream_t s);
+int op_pidi_fuse(const float* const* maps4, int N, int H, int W, const float* par5, int apply_filter, int out_channels, unsigned char* out,
+                 float* logits, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------
 // Grouped launches over sibling problems (round 5). The adapter blocks of one pyramid level are independent and have identical
 // shapes (model/ctrl_adapter.py:181-191 simply runs them one after the other): the plan records the op sequence of every sibling and
 // replays the sequences in lock-step; while a collector is installed, the ops below deposit their arguments instead of launching,

@@ -190,8 +190,9 @@ class HEDdetector:
 
 
 def _extract(frames, detector, scribble, as_pil):
-    if not isinstance(detector, HEDdetector):
-        raise TypeError("a ctrl_adapter_amd.HEDdetector is required (there is no CPU fallback)")
+    from .pidinet import PidiNetDetector
+    if not isinstance(detector, (HEDdetector, PidiNetDetector)):
+        raise TypeError("a ctrl_adapter_amd.HEDdetector or PidiNetDetector is required (there is no CPU fallback)")
     frames = list(frames)
     first = _as_u8_rgb(frames[0]) if frames else None
     res = min(first.shape[:2]) if first is not None else 512
@@ -201,10 +202,15 @@ def _extract(frames, detector, scribble, as_pil):
 
 def extract_scribble(frames, detector, as_pil=False):
     """the `control_type == 'scribble'` branch of ControlNetHelper.prepare_conditioning_images (model/ctrl_helper.py:196-197:
-    HEDdetector(img, scribble=True) per frame) for a whole clip -> uint8 [N, H, W, 3] on the GPU, or the list of PIL images"""
+    HEDdetector(img, scribble=True) per frame) for a whole clip -> uint8 [N, H, W, 3] on the GPU, or the list of PIL images.
+    A PidiNetDetector gives PidiNetDetector(img, scribble=True) instead (the same tail behind PiDiNet's map)."""
     return _extract(frames, detector, True, as_pil)
 
 
 def extract_softedge(frames, detector, as_pil=False):
-    """HED's soft-edge map (HEDdetector(img), the condition of control_v11p_sd15_softedge) for a whole clip"""
+    """the `control_type == 'softedge'` branch of ControlNetHelper.prepare_conditioning_images (model/ctrl_helper.py:184-185) for a whole
+    clip -> uint8 [N, H, W, 3] on the GPU, or the list of PIL images.  The reference's soft-edge detector is PiDiNet: add_softedge_estimator
+    (model/ctrl_helper.py:103-107) overwrites its HEDdetector with PidiNetDetector.from_pretrained('lllyasviel/Annotators'), so pass a
+    ctrl_adapter_amd.PidiNetDetector for the map the released soft-edge adapters were trained on.  An HEDdetector gives HED's soft-edge
+    map (HEDdetector(img), the condition of control_v11p_sd15_softedge), exactly as before."""
     return _extract(frames, detector, False, as_pil)

@@ -883,6 +883,60 @@ int ctrl_op_hed_blur_f32(const void* src_u8, int N, int H, int W, float* out, vo
 int ctrl_op_hed_nms(const float* x, int N, int H, int W, void* out_u8, void* stream);
 int ctrl_op_hed_blur_u8_bin(const void* src_u8, int N, int H, int W, int out_channels, void* out_u8, void* stream);
 
+/* ---- PiDiNet annotator (controlnet_aux PidiNetDetector, pidinet() = PiDiNet(60, 'carv4', dil 24, sa)): the reference's `softedge`
+ * condition (model/ctrl_helper.py:103-107, 184-185) ----
+ * Parameters by the checkpoint's keys with `module.` stripped: init_block.weight [60][3][3][3], block{s}_{j}.conv1.weight [C][1][3][3],
+ * .conv2.weight [Co][C][1][1], .shortcut.weight [Co][C][1][1] / .bias [Co] (the first block of stages 2, 3, 4),
+ * dilations.{i}.conv1.weight [24][C][1][1] / .bias, .conv2_{1..4}.weight [24][24][3][3], attentions.{i}.conv1.weight [4][24][1][1] / .bias,
+ * .conv2.weight [1][4][3][3], conv_reduces.{i}.conv.weight [1][24][1][1] / .bias, classifier.weight [1][4][1][1] / .bias.
+ * Activations are fp16 NHWC with the channels padded 60 -> 64, 120 -> 128, 240 -> 256 (pad channels hold exact zeros); a forward in which
+ * a stored activation leaves the fp16 range returns an error (it reads one flag word back: it synchronises and refuses a capturing stream).
+ *   ws_cap_bytes      the workspace one group of frames may take (0 = 1 GiB); frames_per_group > 0 fixes the group instead (the
+ *                     forward's own argument, when positive, wins).  A frame's result does not depend on its batch or group.
+ * ctrl_pidi_forward: frames uint8 [N][H][W][3] RGB (device), H and W multiples of 64 -> out uint8 [N][H][W] | [N][H][W][3]: the soft edge
+ * map (apply_filter: 255 where the edge is > 0.5, else 0), with scribble != 0 HED's tail behind it; logits (optional, fp32 [N][H][W]): the
+ * classifier's output in front of the sigmoid. */
+typedef struct ctrl_pidi_config {
+    int32_t frames_per_group;
+    int32_t reserved;
+    int64_t ws_cap_bytes;
+} ctrl_pidi_config;
+typedef struct ctrl_pidi ctrl_pidi;   /* opaque */
+int ctrl_pidi_create(const ctrl_pidi_config* cfg, const ctrl_tensor_ref* tensors, int n_tensors, void* stream, ctrl_pidi** out);
+void ctrl_pidi_destroy(ctrl_pidi* h);
+int ctrl_pidi_forward(ctrl_pidi* h, const void* frames_u8, int N, int H, int W, int scribble, int apply_filter, int out_channels, void* out_u8,
+                      float* logits, int frames_per_group, void* stream);
+int64_t ctrl_pidi_ws_bytes(ctrl_pidi* h, int N, int H, int W, int scribble, int frames_per_group);
+/* HOST only.  convert_pdc: a pixel-difference convolution's weight w fp32 [Co][Ci][3][3] -> the vanilla kernel that computes the same
+ * map, out fp32 [Co][Ci][9] (kind 0 cv, 1 cd, 2 ad) or [Co][Ci][25] (kind 3 rd); computed in double, rounded once.
+ * launch_shape: the output tile (pixels) one workgroup owns, kernel 0 = the PDC block, 1 = the context head. */
+int ctrl_pidi_convert_pdc(int kind, const float* w, int Co, int Ci, float* out);
+int ctrl_pidi_launch_shape(int kernel, int* tile_h, int* tile_w);
+/* op level (csrc/pidinet.hip).  CP(C) = C rounded up to 64; every weight below is padded with zeros to these widths.
+ *   stem       src uint8 [N][H][W][3] RGB -> conv3x3(BGR / 255, w) fp16 [N][H][W][64]; w fp32 [9][3][64], tap-major, channel index in the
+ *              NET's (BGR) order; W % 4 == 0
+ *   block      x fp16 [N][H][W][CP(Cin)] -> out fp16 [N][Ho][Wo][CP(Cout)] = conv2(relu(dw(xp))) + skip, xp = x (pool 0, Ho = H) or
+ *              max_pool2d(x, 2, 2) (pool 1, Ho = H / 2); dw fp32 [taps][CP(Cin)], taps 9 (3 x 3) or 25 (the rd footprint: the nine
+ *              positions convert_pdc leaves zero are not read); w2 fp16 [CP(Cout)][CP(Cin)]; skip = xp (wsc NULL; Cin == Cout) or
+ *              wsc . xp + bsc (wsc fp16 [CP(Cout)][CP(Cin)], bsc fp32 [CP(Cout)]).  The input's pad channels are not read as values.
+ *   head_reduce   t fp16 [N][H][W][32] = w1 . relu(x) + b1; w1 fp16 [32][CP(C)], b1 fp32 [32] (rows 24..31 zero)
+ *   head_context  s = the sum of the four dilated 3 x 3 convolutions of t (wd fp16 [36][32][32]: [dilation 5,7,9,11][ky][kx] x cout x cin),
+ *              kept in fp32; a4 fp32 [N][H][W][4] = att . relu(s) + att_b, d fp32 [N][H][W] = red . s; par: HOST fp32 [124] =
+ *              att [4][24] | att_b [4] | red [24]
+ *   side       e fp32 [N][H][W] = sigmoid(conv3x3(a4, w)) * d + b; par: HOST fp32 [37] = w [ky][kx][4] | b
+ *   fuse       maps: HOST array of four device pointers, map k fp32 [N][H >> k][W >> k] -> torch's bilinear (align_corners = False) to
+ *              H x W, logit = cls . e + cls_b (par: HOST fp32 [5]), sigmoid, apply_filter, * 255, clip, truncation; H, W % 8 == 0 */
+int ctrl_op_pidi_stem(const void* src_u8, int N, int H, int W, const float* w, void* out_f16, int32_t* nonfinite, void* stream);
+int ctrl_op_pidi_block(const void* x_f16, int N, int H, int W, int Cin, int Cout, int taps, const float* dw, const void* w2_f16,
+                       const void* wsc_f16, const float* bsc, int pool, void* out_f16, int32_t* nonfinite, void* stream);
+int ctrl_op_pidi_head_reduce(const void* x_f16, int N, int H, int W, int C, const void* w1_f16, const float* b1, void* t_f16,
+                             int32_t* nonfinite, void* stream);
+int ctrl_op_pidi_head_context(const void* t_f16, int N, int H, int W, const void* wd_f16, const float* par_host124, float* a4, float* d,
+                              void* stream);
+int ctrl_op_pidi_side(const float* a4, const float* d, int N, int H, int W, const float* par_host37, float* e, void* stream);
+int ctrl_op_pidi_fuse(const float* const* maps, int N, int H, int W, const float* par_host5, int apply_filter, int out_channels,
+                      void* out_u8, float* logits, void* stream);
+
 /* ---- SVD backbone UNet(diffusers UNetSpatioTemporalConditionModel with the reference's two ControlNet-residual kwargs) ---- */
 typedef struct ctrl_unet_st_config {
     int32_t in_channels;                           /* 8 */
