@@ -6,6 +6,8 @@ float32; then repeats the frames batch_size * num_images_per_prompt times (:284-
 to `dtype` and duplicates for classifier-free guidance (:291-294).  Here the uint8 frames go to the GPU once and two HIP
 kernels (csrc/imageprep.hip) do Pillow's 8-bit separable Lanczos resampling -- bit-exact, it is integer arithmetic --
 the /255, the layout change and every replica in one sweep.  Same signature and return value as the reference method.
+The horizontal pass always runs first; Pillow 12.2.0 runs the vertical pass first on very tall slivers whose two axes both
+resample (1000 x 3 -> 8 x 8; no such source below Hin = 32 Win was found), where the bytes then differ.
 The 22-bit fixed-point weight tables of Pillow's precompute_coeffs are computed on the host in double precision and cached
 per (input size, output size).
 """

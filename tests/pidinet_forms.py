@@ -12,8 +12,8 @@ IDENTITY_WIDTHS = ((60, 60), (120, 120), (240, 240))
 POOL_WIDTHS = ((60, 120), (120, 240), (240, 240))
 BATCHES = (1, 3)
 HEAD_WIDTHS = (60, 120, 240)
-FUSE_SIZES = ((64, 64), (64, 128))
-DETECTOR_CASES = {"64x64": (1, 64, 64), "64x128": (2, 64, 128)}
+FUSE_SIZES = ((64, 64), (64, 128), (128, 64))          # (128, 64): a tall map
+DETECTOR_CASES = {"64x64": (1, 64, 64), "64x128": (2, 64, 128), "128x64": (2, 128, 64)}
 PAD_GARBAGE = 777.0                     # finite; what an input's pad channels hold in the second run of a block form
 
 

@@ -238,7 +238,7 @@ def bounded(gpu):
     """the bounded checkpoint, its frames and the fp64 logits + bounds, computed once"""
     sd = R.make_state_dict(3, "bounded")
     cases = {}
-    for key, (N, H, W) in {"one": (1, 64, 64), "three": (3, 64, 128)}.items():
+    for key, (N, H, W) in {"one": (1, 64, 64), "three": (3, 64, 128), "tall": (2, 128, 64), "taller": (1, 192, 64)}.items():
         frames = R.make_frames(5, N, H, W)
         logit, bound = R.logits_and_bound(sd, frames)
         cases[key] = (frames, logit.numpy(), bound.numpy())
@@ -270,6 +270,16 @@ def test_detector_within_the_derived_bound(gpu, bounded):
     soft = _check_detector(det, *cases["one"], None, "64x64 N=1")
     assert len(np.unique(soft)) > 20                       # the map is not flat: the interval check says something
     _check_detector(det, *cases["three"], 2, "64x128 N=3 in groups of 2")
+
+
+def test_tall_frames_within_the_derived_bound(gpu, bounded):
+    """two and three tile rows of the blur, H > W in the fuse, one frame per group: the same derived bound"""
+    import ctrl_adapter_amd as P
+    sd, cases = bounded
+    det = P.HEDdetector.from_state_dict(sd, device=gpu)
+    soft = _check_detector(det, *cases["tall"], 1, "128x64 N=2 in groups of 1")
+    assert len(np.unique(soft)) > 20
+    _check_detector(det, *cases["taller"], 1, "192x64 N=1 in groups of 1")
 
 
 def test_scale_lever_stays_within_the_bound(gpu, bounded):
@@ -305,6 +315,24 @@ def test_frames_do_not_depend_on_batch_or_group(gpu):
             assert torch.equal(det.run(frames, return_logits=True, frames_per_group=2)[1], wl)
     assert det.workspace_bytes(3, 64, 128, frames_per_group=1) < det.workspace_bytes(3, 64, 128, frames_per_group=2) \
         <= det.workspace_bytes(3, 64, 128)
+
+
+def test_tall_frames_do_not_depend_on_batch_or_group(gpu):
+    """128 x 64: two tile rows of the blur per frame, H > W in the fuse"""
+    import ctrl_adapter_amd as P
+    det = P.HEDdetector.from_state_dict(R.make_state_dict(31, "he"), device=gpu)
+    frames = R.make_frames(11, 3, 128, 64).to(gpu)
+    for scribble in (False, True):
+        whole = det.run(frames, scribble=scribble)
+        for n in range(3):
+            alone = det.run(frames[n:n + 1], scribble=scribble)
+            assert torch.equal(alone[0], whole[n]), "frame %d: %d bytes differ between N = 1 and N = 3" % (n, int((alone[0] != whole[n]).sum()))
+        for fpg in (1, 2):
+            again = det.run(frames, scribble=scribble, frames_per_group=fpg)
+            assert torch.equal(again, whole), "frames_per_group=%d: %d bytes differ" % (fpg, int((again != whole).sum()))
+    wl = det.run(frames, return_logits=True)[1]
+    assert float(wl.std()) > 0.3 and torch.equal(det.run(frames, return_logits=True, frames_per_group=1)[1], wl)
+    assert torch.equal(det.run(frames[2:3], return_logits=True)[1][0], wl[2])
 
 
 def test_range_guard(gpu):
