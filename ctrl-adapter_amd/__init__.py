@@ -9,6 +9,7 @@ from .image_prep import prepare_images  # noqa: F401
 from .canny import canny, extract_canny  # noqa: F401  (the name `canny` is the function; the module stays importable as ctrl_adapter_amd.canny)
 from .hed import HEDdetector, extract_scribble, extract_softedge  # noqa: F401
 from .pidinet import PidiNetDetector, pidinet_state_dict_spec  # noqa: F401
+from .lineart import LineartDetector, extract_lineart, lineart_state_dict_spec  # noqa: F401
 from .text_encoder import CLIPTextModel, CLIPTextOutput, encode_controlnet_prompt  # noqa: F401
 from .text_encoder import CLIPTextModelWithProjection, CLIPTextModelOutput, encode_sdxl_prompt  # noqa: F401
 from .vision_encoder import CLIPVisionModelWithProjection, CLIPVisionModelOutput, encode_i2vgen_image, encode_svd_image  # noqa: F401

@@ -176,6 +176,10 @@ class PidiConfig(C.Structure):
     _fields_ = [("frames_per_group", C.c_int32), ("reserved", C.c_int32), ("ws_cap_bytes", C.c_int64)]
 
 
+class LineartConfig(C.Structure):
+    _fields_ = [("frames_per_group", C.c_int32), ("has_coarse", C.c_int32), ("ws_cap_bytes", C.c_int64)]
+
+
 U8_NHWC = 3     # pixel dtype of ctrl_vision_encoder_forward / the vision ops: uint8 [N][H][W][3]
 
 
@@ -241,6 +245,9 @@ EXPORTS = [
     "ctrl_pidi_create", "ctrl_pidi_destroy", "ctrl_pidi_forward", "ctrl_pidi_ws_bytes", "ctrl_pidi_convert_pdc", "ctrl_pidi_launch_shape",
     "ctrl_op_pidi_stem", "ctrl_op_pidi_block", "ctrl_op_pidi_head_reduce", "ctrl_op_pidi_head_context", "ctrl_op_pidi_side",
     "ctrl_op_pidi_fuse",
+    "ctrl_lineart_create", "ctrl_lineart_destroy", "ctrl_lineart_forward", "ctrl_lineart_ws_bytes", "ctrl_lineart_launch_shape",
+    "ctrl_op_lineart_stem", "ctrl_op_in_stats_ws_floats", "ctrl_op_in_stats", "ctrl_op_in_apply", "ctrl_op_lineart_head",
+    "ctrl_op_pack_convt_w_phase", "ctrl_op_pack_convt_w_phase_ovf",
 ]
 
 _lib = None
@@ -262,7 +269,8 @@ def lib():
                             "ctrl_text_encoder_destroy", "ctrl_vision_encoder_destroy", "ctrl_vae_encoder_destroy", "ctrl_vae_decoder_destroy",
                             "ctrl_vae_tdecoder_destroy", "ctrl_unet_st_destroy", "ctrl_unet2d_destroy", "ctrl_unet2d_workspace_bytes",
                             "ctrl_unet_i2v_destroy", "ctrl_unet_i2v_workspace_bytes", "ctrl_sampler_destroy", "ctrl_sampler_scalars",
-                            "ctrl_canny_ws_bytes", "ctrl_hed_destroy", "ctrl_hed_ws_bytes", "ctrl_pidi_destroy", "ctrl_pidi_ws_bytes"):
+                            "ctrl_canny_ws_bytes", "ctrl_hed_destroy", "ctrl_hed_ws_bytes", "ctrl_pidi_destroy", "ctrl_pidi_ws_bytes",
+                            "ctrl_lineart_destroy", "ctrl_lineart_ws_bytes", "ctrl_op_in_stats_ws_floats"):
                 fn.restype = C.c_int
         _lib.ctrl_policy_get.restype = C.c_char_p
         _lib.ctrl_policy_get.argtypes = [C.c_char_p]
@@ -426,6 +434,24 @@ def lib():
         _lib.ctrl_op_pidi_side.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
         _lib.ctrl_op_pidi_fuse.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p,
                                            C.c_void_p, C.c_void_p]
+        _lib.ctrl_lineart_create.argtypes = [C.POINTER(LineartConfig), C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
+        _lib.ctrl_lineart_destroy.restype = None
+        _lib.ctrl_lineart_destroy.argtypes = [C.c_void_p]
+        _lib.ctrl_lineart_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_int, C.c_void_p]
+        _lib.ctrl_lineart_ws_bytes.restype = C.c_int64
+        _lib.ctrl_lineart_ws_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+        _lib.ctrl_lineart_launch_shape.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        _lib.ctrl_op_lineart_stem.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ctrl_op_in_stats_ws_floats.restype = C.c_int64
+        _lib.ctrl_op_in_stats_ws_floats.argtypes = [C.c_int, C.c_int, C.c_int]
+        _lib.ctrl_op_in_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ctrl_op_in_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_int,
+                                          C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ctrl_op_lineart_head.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]
+        _lib.ctrl_op_pack_convt_w_phase.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        _lib.ctrl_op_pack_convt_w_phase_ovf.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _lib.ctrl_rccl_comm_destroy.restype = None
         _lib.ctrl_rccl_comm_destroy.argtypes = [C.c_void_p]
         _lib.ctrl_rccl_comm_bytes_sent.restype = C.c_int64

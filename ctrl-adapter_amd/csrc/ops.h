@@ -406,6 +406,23 @@ int op_pidi_fuse(const float* const* maps4, int N, int H, int W, const float* pa
                  float* logits, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
+// Lineart annotator (lineart.hip; controlnet_aux LineartDetector: the `lineart` branch of model/ctrl_helper.py:111-114, 190-191).
+// Layouts and semantics: include/ctrl_hip.h (ctrl_op_lineart_*, ctrl_op_in_*).
+// ------------------------------------------------------------------------------------------
+// kernel 0 stem / 1 head: the output tile (rows, columns) of one workgroup; 2: rows of an image one workgroup of in_stats reduces (C given), 1
+void lineart_launch_shape(int kernel, int C, int* a, int* b);
+int op_lineart_stem(const unsigned char* src, int N, int H, int W, const float* w, half_t* out, int32_t* nonfinite, hipStream_t s);
+// floats of scratch op_in_stats needs (the per-workgroup partials); 0 = a shape it refuses
+size_t op_in_stats_ws_floats(int N, int HW, int C);
+int op_in_stats(const half_t* x, int N, int HW, int C, float* stats, float* ws, hipStream_t s);
+int op_in_apply(const half_t* x, const float* stats, int N, int H, int W, int C, float eps, int relu, const half_t* res, int res_pad, int pad,
+                half_t* out, int32_t* nonfinite, hipStream_t s);
+int op_lineart_head(const half_t* xp, int N, int H, int W, const float* w, float bias, int out_channels, unsigned char* out, float* logits,
+                    hipStream_t s);
+// ConvTranspose2d(3, stride 2, padding 1, output_padding 1) weight [Cin][Cout][3][3] -> the phase pack fp16 [4][Cout][4][Cin] (IG_CONV2D_PHASE)
+int op_pack_convT_w_phase(const void* w, int dtype, half_t* out, int Cin, int Cout, hipStream_t s, int* ovf = nullptr);
+
+// ------------------------------------------------------------------------------------------
 // Grouped launches over sibling problems (round 5). The adapter blocks of one pyramid level are independent and have identical
 // shapes (model/ctrl_adapter.py:181-191 simply runs them one after the other): the plan records the op sequence of every sibling and
 // replays the sequences in lock-step; while a collector is installed, the ops below deposit their arguments instead of launching,

@@ -696,6 +696,56 @@ def merge_gather_launch_shape(slots, outs, weights=None, rows=None, widx=None, f
     return b.value, v.value, cap.value
 
 
+# ---- the lineart annotator's kernels (csrc/lineart.hip; include/ctrl_hip.h: ctrl_op_lineart_*, ctrl_op_in_*) ----
+def pack_convT_w_phase(w, ovf=None):
+    """ConvTranspose2d(3, stride 2, padding 1, output_padding 1) weight [Cin][Cout][3][3] -> fp16 [4][Cout][4*Cin]: the W operand of an
+    IG_CONV2D_PHASE problem over the source map"""
+    cin, cout = w.shape[0], w.shape[1]
+    assert tuple(w.shape[2:]) == (3, 3)
+    out = _f16(4, cout, 4 * cin, device=w.device)
+    if ovf is not None:
+        L.check(L.lib().ctrl_op_pack_convt_w_phase_ovf(L.ptr(w.contiguous()), L.dtype_code(w.dtype), L.ptr(out), cin, cout, L.ptr(ovf), L.cur_stream()))
+        return out
+    L.check(L.lib().ctrl_op_pack_convt_w_phase(L.ptr(w.contiguous()), L.dtype_code(w.dtype), L.ptr(out), cin, cout, L.cur_stream()))
+    return out
+
+
+def lineart_launch_shape(kernel, Cc=0):
+    a, b = C.c_int(), C.c_int()
+    L.check(L.lib().ctrl_lineart_launch_shape(int(kernel), int(Cc), C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def lineart_stem_into(src_u8, w_packed, out, flag=None):
+    """src uint8 [N][H][W][3], w fp32 [49][3][64] -> out fp16 [N][H][W][64]"""
+    N, H, W = src_u8.shape[:3]
+    L.check(L.lib().ctrl_op_lineart_stem(L.ptr(src_u8), N, H, W, L.ptr(w_packed), L.ptr(out), L.ptr(flag), L.cur_stream()))
+
+
+def in_stats_ws_floats(N, HW, Cc):
+    """floats of scratch in_stats_into needs (0: a shape it refuses)"""
+    return int(L.lib().ctrl_op_in_stats_ws_floats(int(N), int(HW), int(Cc)))
+
+
+def in_stats_into(x, N, HW, Cc, stats, ws=None):
+    """x fp16 [N][HW][C] -> stats fp32 [N][C][2] = (sum, sum of squares)"""
+    if ws is None:
+        ws = torch.empty(in_stats_ws_floats(N, HW, Cc) + 4, dtype=torch.float32, device=x.device)
+    L.check(L.lib().ctrl_op_in_stats(L.ptr(x), N, HW, Cc, L.ptr(stats), L.ptr(ws), L.cur_stream()))
+
+
+def in_apply_into(x, stats, N, H, W, Cc, out, pad=0, relu=False, res=None, res_pad=0, eps=1e-5, flag=None):
+    """InstanceNorm apply: out fp16 [N][H + 2 pad][W + 2 pad][C] (reflection padding written out)"""
+    L.check(L.lib().ctrl_op_in_apply(L.ptr(x), L.ptr(stats), N, H, W, Cc, float(eps), int(bool(relu)), L.ptr(res), int(res_pad), int(pad),
+                                     L.ptr(out), L.ptr(flag), L.cur_stream()))
+
+
+def lineart_head_into(xp, N, H, W, w_packed, bias, out, logits=None):
+    """xp fp16 [N][H + 6][W + 6][64], w fp32 [49][64] -> out uint8 [N][H][W] | [N][H][W][3] (+ fp32 logits)"""
+    ch = 3 if out.dim() == 4 else 1
+    L.check(L.lib().ctrl_op_lineart_head(L.ptr(xp), N, H, W, L.ptr(w_packed), float(bias), ch, L.ptr(out), L.ptr(logits), L.cur_stream()))
+
+
 _profiling = False
 
 

@@ -937,6 +937,58 @@ int ctrl_op_pidi_side(const float* a4, const float* d, int N, int H, int W, cons
 int ctrl_op_pidi_fuse(const float* const* maps, int N, int H, int W, const float* par_host5, int apply_filter, int out_channels,
                       void* out_u8, float* logits, void* stream);
 
+/* ---- Lineart annotator (controlnet_aux LineartDetector: two Generator(3, 1, 3) nets, sk_model.pth and sk_model2.pth for coarse): the
+ * reference's `lineart` condition (model/ctrl_helper.py:111-114, 190-191) ----
+ * Parameters by the checkpoints' keys under the prefix `fine.` (and `coarse.` when has_coarse != 0), weight and bias each:
+ * model0.1 [64][3][7][7], model1.0 [128][64][3][3], model1.3 [256][128][3][3], model2.{0,1,2}.conv_block.{1,5} [256][256][3][3],
+ * model3.0 [256][128][3][3] and model3.3 [128][64][3][3] (ConvTranspose2d: [Cin][Cout][3][3]), model4.1 [1][64][7][7].  Every norm is
+ * InstanceNorm2d without affine parameters (eps 1e-5, biased variance), so every bias but model4.1's cancels and is dropped at load; all
+ * of them must still be present and well-shaped.  Activations are fp16 NHWC; a forward in which a stored activation leaves the fp16 range
+ * returns an error (it reads one flag word back: it synchronises and refuses a capturing stream).
+ *   ws_cap_bytes      the workspace one group of frames may take (0 = 1 GiB; one 512 x 512 frame needs about 105 MB); frames_per_group > 0
+ *                     fixes the group instead (the forward's own argument, when positive, wins).  A frame's result does not depend on its
+ *                     batch or group.
+ * ctrl_lineart_forward: frames uint8 [N][H][W][3] RGB (device), H and W multiples of 64 -> out uint8 [N][H][W] | [N][H][W][3]:
+ * 255 - uint8(clip(255 sigmoid(logit))) (truncation); coarse != 0 runs the coarse generator; logits (optional, fp32 [N][H][W]): model4.1's
+ * output in front of the sigmoid. */
+typedef struct ctrl_lineart_config {
+    int32_t frames_per_group;
+    int32_t has_coarse;
+    int64_t ws_cap_bytes;
+} ctrl_lineart_config;
+typedef struct ctrl_lineart ctrl_lineart;   /* opaque */
+int ctrl_lineart_create(const ctrl_lineart_config* cfg, const ctrl_tensor_ref* tensors, int n_tensors, void* stream, ctrl_lineart** out);
+void ctrl_lineart_destroy(ctrl_lineart* h);
+int ctrl_lineart_forward(ctrl_lineart* h, const void* frames_u8, int N, int H, int W, int coarse, int out_channels, void* out_u8, float* logits,
+                         int frames_per_group, void* stream);
+int64_t ctrl_lineart_ws_bytes(ctrl_lineart* h, int N, int H, int W, int frames_per_group);
+/* HOST only.  kernel 0 (stem) and 1 (head): the output tile one workgroup owns, *a rows by *b columns; kernel 2 (in_stats): *a = the rows
+ * of an image one workgroup reduces for maps of C channels, *b = 1. */
+int ctrl_lineart_launch_shape(int kernel, int C, int* a, int* b);
+/* op level (csrc/lineart.hip).
+ *   stem       src uint8 [N][H][W][3] RGB -> conv7x7(reflect_pad3(x / 255), w) fp16 [N][H][W][64]; w fp32 [49][3][64] (tap-major: ky, kx,
+ *              then the input channel); no bias; H, W >= 4
+ *   in_stats   x fp16 [N][HW][C] (C = 8 .. 256, a power of two) -> stats fp32 [N][C][2] = (sum, sum of squares) over the HW rows, in a
+ *              fixed order; ws: ctrl_op_in_stats_ws_floats(N, HW, C) floats of scratch
+ *   in_apply   y = (x - mean) * rsqrt(var + eps), mean = sum / HW, var = max(sumsq / HW - mean^2, 0); ReLU when relu != 0; + res when
+ *              given; out fp16 [N][H + 2 pad][W + 2 pad][C], pad 0 | 1 | 3: the map with its reflection padding (no edge repeat)
+ *              written out; res fp16 [N][H + 2 res_pad][W + 2 res_pad][C] is read at its interior
+ *   head       xp fp16 [N][H + 6][W + 6][64] (reflect-padded by 3) -> logit = conv7x7(xp, w) + bias (w fp32 [49][64], tap-major) ->
+ *              out uint8 [N][H][W] | [N][H][W][3] = 255 - uint8(min(255, 255 sigmoid(logit))); logits (optional) fp32 [N][H][W]
+ *   pack_convT_w_phase  ConvTranspose2d(3, stride 2, padding 1, output_padding 1) weight [Cin][Cout][3][3] (any dtype) -> fp16
+ *              [4][Cout][4][Cin], the weight pack of ctrl_igemm_desc::mode 3: phase 2a + b, tap 2ty + tx takes w[ci][co][ky][kx] with
+ *              (a, ty) -> ky: (0,0) none (zero), (0,1) 1, (1,0) 2, (1,1) 0 and the same for (b, tx) -> kx; _ovf also raises *ovf (device)
+ *              when a value does not fit fp16 */
+int ctrl_op_lineart_stem(const void* src_u8, int N, int H, int W, const float* w, void* out_f16, int32_t* nonfinite, void* stream);
+int64_t ctrl_op_in_stats_ws_floats(int N, int HW, int C);
+int ctrl_op_in_stats(const void* x_f16, int N, int HW, int C, float* stats, float* ws, void* stream);
+int ctrl_op_in_apply(const void* x_f16, const float* stats, int N, int H, int W, int C, float eps, int relu, const void* res_f16, int res_pad,
+                     int pad, void* out_f16, int32_t* nonfinite, void* stream);
+int ctrl_op_lineart_head(const void* xp_f16, int N, int H, int W, const float* w, float bias, int out_channels, void* out_u8, float* logits,
+                         void* stream);
+int ctrl_op_pack_convt_w_phase(const void* w, int dtype, void* out, int Cin, int Cout, void* stream);
+int ctrl_op_pack_convt_w_phase_ovf(const void* w, int dtype, void* out, int Cin, int Cout, int32_t* ovf, void* stream);
+
 /* ---- SVD backbone UNet(diffusers UNetSpatioTemporalConditionModel with the reference's two ControlNet-residual kwargs) ---- */
 typedef struct ctrl_unet_st_config {
     int32_t in_channels;                           /* 8 */
